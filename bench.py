@@ -25,6 +25,16 @@ Launch:  python bench.py --gpus N --steps K --warmup W
     child process, started before anything here touches the GPU), relays rank 0's line and
     exits with the children's code.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`,
+`ms_per_step`, ...).  Everything else it can measure is behind --full: per-kernel times and the
+rooflines (HIP events in the timed region + a second, untimed pass), b100 / b200, the autograd
+route, config 5, the CPU baseline, and at N > 1 the collective probe and the strong-scaling pass
+over 20 000 paths; the --no-* switches drop single extras of a --full run.
+--dump-outputs DIR: rank 0 writes what the last timed step computed -- loss.npy (float64 [1]),
+grad.npy (flat gradient, float32 [P]) and params.npy (parameters after the Adam step, float32
+[P]) -- so that two builds can be compared output for output (the inputs and the initialisation
+are seeded: identical from run to run with the same arguments).
 """
 import argparse
 import contextlib
@@ -527,6 +537,13 @@ def main():
     ap.add_argument('--global-paths', type=int, default=0,
                     help='strong scaling: the ranks share this many paths (e.g. 1000000 on 8 GPUs)')
     ap.add_argument('--dropout', type=float, default=0.1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the extras outside the headline (per-kernel times, rooflines, '
+                         'b100 / b200, autograd route, config 5, CPU baseline; N > 1: collective '
+                         'probe, strong-scaling pass); off: the headline steps only')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes the last timed step\'s loss, flat gradient and updated '
+                         'parameters as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-small-batch', action='store_true')
@@ -621,7 +638,8 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    timing = not args.no_kernel_timing and world == 1   # per-kernel times / roofline: N = 1 only
+    # per-kernel times / roofline: N = 1, --full only
+    timing = args.full and not args.no_kernel_timing and world == 1
     sync()
     # HIP events inside the timed region: around the DOMINANT kernel only (the ODE backward) --
     # bracketing all six hot kernels costs ~3.5 % of the step.  The other kernels' times come
@@ -637,6 +655,12 @@ def main():
     opt.time_allreduce = False
     allreduce_ms = opt.allreduce_ms()
     flat_after = model.flat_parameters().detach().clone()   # parameters after warmup + K steps
+    if args.dump_outputs and rank == 0:                     # what the last timed step computed
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outputs = {'loss': loss.detach().reshape(1).to(torch.float64),
+                   'grad': model.flat_grad().detach(), 'params': flat_after}
+        for name, v in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), v.cpu().numpy())
     kern, kern_timed = {}, {}
     if timing:
         _lib.profile_enable(False)
@@ -672,9 +696,9 @@ def main():
     if args.dump_params and rank == 0:
         np.save(args.dump_params, flat.cpu().numpy())
 
-    comm = comm_probe(model, dev, world, step_args) if distributed else None
+    comm = comm_probe(model, dev, world, step_args) if distributed and args.full else None
     strong20 = None
-    if distributed and not strong and not args.no_strong_20k:
+    if distributed and args.full and not strong and not args.no_strong_20k:
         strong20 = strong_scaling_20k(model, opt, dev, world, rank, args.steps, min(args.warmup, 10), prefetch)
 
     if rank == 0:
@@ -775,14 +799,14 @@ def main():
                                  'unit': 'TFLOP/s', 'frac': round(tf / FP32_MFMA_PEAK_TF, 5),
                                  'useful_flops_per_step': int(flops),
                                  'note': 'whole step incl. plan, reductions, Adam, launches'}
-        if world == 1 and not args.no_small_batch:
+        if world == 1 and args.full and not args.no_small_batch:
             model._plans.clear()
             sb = small_batch_ms(model, opt, dev, dt, T, prefetch=prefetch)
             out['b100_ms'] = round(sb[100], 4)
             out['b200_ms'] = round(sb[200], 4)
             out['b100_paths_per_s'] = round(100 / (sb[100] * 1e-3), 1)
             out['b200_paths_per_s'] = round(200 / (sb[200] * 1e-3), 1)
-        if world == 1 and not args.no_autograd_route:
+        if world == 1 and args.full and not args.no_autograd_route:
             model._plans.clear()
             out['autograd_route_ms'] = round(autograd_route_ms(dev, dt, T, step_args, args.dropout,
                                                                args.steps), 4)
@@ -792,7 +816,7 @@ def main():
             args100 = (b100['times'], b100['time_ptr'], b100['X'].to(dev), b100['obs_idx'].to(dev, torch.int32),
                        dt, T, b100['start_X'].to(dev), b100['n_obs_ot'].to(dev, torch.int32))
             out['autograd_route_b100_ms'] = round(autograd_route_ms(dev, dt, T, args100, args.dropout, 50), 4)
-        if world == 1 and not args.no_config5:
+        if world == 1 and args.full and not args.no_config5:
             c5 = config5_ms(dev, args.dropout)
             for bsz, v in c5.items():
                 out['c5_b{}_ms'.format(bsz)] = v['ms']
@@ -802,7 +826,7 @@ def main():
                               'strict_flops_note': '2 x 8 750 MAC x 3 (fwd + bwd) x Euler steps x paths (SURVEY 8d)',
                               'peak_tflops': FP32_MFMA_PEAK_TF,
                               **{'b{}'.format(k): v for k, v in c5.items()}}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             with contextlib.redirect_stdout(sys.stderr):
                 out['cpu_baseline'] = cpu_baseline(dt, T)
         print(json.dumps(out), flush=True)   # the ONE line on stdout

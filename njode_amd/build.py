@@ -200,7 +200,9 @@ def build(force=False, jobs=None, verbose=True):
         if verbose:
             print('[njode_amd.build] up to date:', LIB)
         return LIB
-    jobs = jobs or int(os.environ.get('NJODE_BUILD_JOBS', os.cpu_count() or 4))
+    # (MAX_JOBS / the affinity mask: what this process may use, not the whole host's core count)
+    jobs = jobs or int(os.environ.get('NJODE_BUILD_JOBS') or os.environ.get('MAX_JOBS')
+                       or len(os.sched_getaffinity(0)) or 4)
     if verbose:
         print('[njode_amd.build] compiling {} of {} units for {} with {} jobs ...'.format(
             len(todo), len(tasks), ARCH, jobs))

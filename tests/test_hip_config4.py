@@ -64,7 +64,7 @@ def _check_pair(two, p2, one, p1, global_batch, scaling):
 
 
 def test_bench_self_spawns_two_ranks_weak_scaling(tmp_path):
-    two, p2 = _bench(tmp_path, 'weak2', 2, ['--paths-per-gpu', '20000'], share=True)
+    two, p2 = _bench(tmp_path, 'weak2', 2, ['--paths-per-gpu', '20000', '--full'], share=True)
     one, p1 = _bench(tmp_path, 'weak1', 1, ['--paths-per-gpu', '40000', '--no-kernel-timing'],
                      share=False)
     assert one['n_gpus'] == 1 and 'rccl_world' not in one
@@ -77,7 +77,7 @@ def test_bench_self_spawns_two_ranks_weak_scaling(tmp_path):
 
 def test_bench_self_spawns_two_ranks_strong_scaling_at_config4_shard_size(tmp_path):
     g = 2 * SHARD
-    two, p2 = _bench(tmp_path, 'strong2', 2, ['--global-paths', str(g)], share=True)
+    two, p2 = _bench(tmp_path, 'strong2', 2, ['--global-paths', str(g), '--full'], share=True)
     one, p1 = _bench(tmp_path, 'strong1', 1, ['--global-paths', str(g), '--no-kernel-timing'],
                      share=False)
     assert two['config']['paths_rank0'] == SHARD

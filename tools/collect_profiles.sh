@@ -2,7 +2,6 @@
 # copy the round's judged artifacts from gpurun_out/ (scratch) into profiles/ (tracked)
 set -e
 R=${1:-r06}
-cp gpurun_out/${R}_final_bench.json profiles/${R}_final_bench.json
 cp gpurun_out/${R}_final_kernel_stats.csv profiles/${R}_final_kernel_stats.csv
 cp gpurun_out/${R}_final_pmc_summary.json profiles/${R}_final_pmc_summary.json
 cp gpurun_out/${R}_final_trace_trace.txt profiles/${R}_final_step_timeline.txt

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiling recipe of the headline bench (run on the GPU box from the repo root):
 #   bash tools/profile_recipe.sh <tag>          e.g. tag = r03_final
-# 1. rocprofv3 --kernel-trace --stats of `python3 bench.py` (the driver's command)
+# 1. rocprofv3 --kernel-trace --stats of `python3 bench.py --full` (kernel_ms and roofline in its line)
 # 2. PMC passes, ONE counter group per pass, kernels of the training step only, 3 steps:
 #    SQ group a / SQ group b / GRBM_GUI_ACTIVE (clock) / FETCH_SIZE / WRITE_SIZE
 #    (FETCH_SIZE and WRITE_SIZE need 3 + 2 of the 4 TCC slots: never in one pass)
@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="$ROOT/bench.py --no-cpu-baseline --no-small-batch --no-autograd-route --no-config5"
 REGEX='k_ode|k_jump|k_encode|k_reduce|k_adam|k_pack|k_row_time|k_dense|k_traj|k_sum'
 
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $BENCH --steps 20 \
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $BENCH --full --steps 20 \
   > $OUT/stats_bench.json 2> $OUT/stats.err
 
 pmc() {   # name, counters...

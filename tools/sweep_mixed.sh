@@ -2,7 +2,7 @@
 # Sweep of the mixed ODE kernels' grid / cost-model constants on the headline workload
 # (run on the GPU box from the repo root): one bench line per setting, kernel_ms inside.
 run() {
-  env "$@" python3 bench.py --no-cpu-baseline --no-small-batch --steps 20 2>/dev/null | \
+  env "$@" python3 bench.py --full --no-cpu-baseline --no-small-batch --steps 20 2>/dev/null | \
     python3 -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms']; print(json.dumps({'env': sys.argv[1:], 'ms_per_step': d['ms_per_step'], 'bwd': k.get('k_ode_bwd_mixed'), 'fwd': k.get('k_ode_fwd_mfma', k.get('k_ode_fwd_mixed'))}))" "$@"
 }
 run A=0
