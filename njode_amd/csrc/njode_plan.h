@@ -120,7 +120,10 @@ __device__ inline void plan_sync(unsigned* ctr, unsigned base, int P, unsigned* 
 // Trajectory layout + split points from the length histogram (one workgroup of NT threads).
 // cnt_s = #{len > s}; base_s = exclusive prefix sum of cnt; base16_s the same with every count rounded
 // up to a whole tile; base_s[K+1], [K+2] = split points T of the mixed ODE backward / forward.
-// lds: SPLIT_KMAX + 1 + 64 ints when K <= SPLIT_KMAX is to take the workgroup scans (lds_cnt), else unused.
+// lds: traj_layout_lds_ints(K, NT) ints when the workgroup scans are taken (lds_cnt), else unused.
+// Ints of lds the body uses with lds_cnt at K <= kmax: cnt[K + 1], padded to 8 bytes, then wsum[NWV]
+// (long long), best_c[2 NWV], best_t[2 NWV].
+constexpr int traj_layout_lds_ints(int kmax, int nt) { return ((kmax + 2) & ~1) + 6 * (nt / 64); }
 template <int NT, bool COH = false>
 __device__ inline void traj_layout_body(const int* len_hist, int n_obs, int K, long long* base_s,
                                         long long* base16_s, const SplitCfg& sc, int* lds, bool lds_cnt) {
@@ -464,6 +467,7 @@ __device__ inline void plan_grid_stages(const PlanJob& j, int pb, int* lds) {
       }
     }
     __syncthreads();                           // (P == 1: the counters above live in the same LDS)
+    static_assert(traj_layout_lds_ints(PLAN_KEYS - 1, NT) <= PLAN_LDS_INTS, "layout tables exceed the plan's LDS");
     traj_layout_body<NT, COH>(j.len_hist, n, K, j.base_s, j.base16_s, j.sc, lds, true);
     if (P > 1) {
       stamp(3);

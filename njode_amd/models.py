@@ -957,7 +957,8 @@ class NJODE(torch.nn.Module):
                       M=None, plan=None):
         """Forward + exact gradient in two library calls, no autograd bookkeeping:
         returns ``(None, loss)`` (device loss tensor; hT is not computed -- it would
-        cost a per-path tail evolve nobody reads) and fills ``flat_grad()`` (whose
+        cost a per-path tail evolve nobody reads; masked and ``use_rnn`` models, whose
+        lockstep plan produces it anyway, return it) and fills ``flat_grad()`` (whose
         slices are the parameters' ``.grad``).  The calls carry ``NJODE_C_LOSS_IN_BWD``:
         on the segment plan the forward skips its readout/loss pass over the observation
         rows and the backward, which evaluates the same readouts anyway, writes the loss.
@@ -967,16 +968,16 @@ class NJODE(torch.nn.Module):
         stream = torch.cuda.current_stream(dev)      # (one lookup per step: ~7 us each)
         call, sched, slot_i, B = self._make_call(
             times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot, False, True, False,
-            M, save_bwd=True, plan_key=(obs_idx, time_ptr), want_hT=self.masked, plan=plan,
+            M, save_bwd=True, plan_key=(obs_idx, time_ptr), want_hT=self.masked or self.use_rnn, plan=plan,
             stream=stream)
         # (always written: sum of the terms; data parallel: written INTO the gradient bucket, see
         # loss_slot())
         loss = (self.loss_slot() if self.dp_loss_in_bucket
                 else torch.empty(1, dtype=torch.float32, device=dev))
-        # hT is only skipped on the segment plan (unmasked): there it would cost an extra
-        # per-path tail evolve; the lockstep plan produces it anyway
+        # hT is only skipped on the segment plan (unmasked, no GRU jump): there it would cost an
+        # extra per-path tail evolve; the lockstep plan (masked, use_rnn) produces it anyway
         hT = (torch.empty(B, self.hidden_size, dtype=torch.float32, device=dev)
-              if self.masked else None)
+              if self.masked or self.use_rnn else None)
         call.flags |= _lib.C_LOSS_IN_BWD
         self._last_stream = stream
         try:

@@ -71,3 +71,47 @@ def bs_batch(n_paths, seed=0, name='BlackScholes', obs_perc=0.1, nb_steps=100):
 
 def grads_by_name(m):
     return {k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters()}
+
+
+def exact_k_batch(n_paths, n_steps, obs_per_path=4, seed=0, d=1):
+    """Demo-shaped unmasked batch whose segment-plan call takes EXACTLY ``n_steps`` Euler steps: the
+    grid step is 2**-10, so every observation time k * dt is exact in float64 and the schedule walks
+    full steps onto it; path 0 is observed at the last grid point (no tail).  Returns (batch, dt, T)."""
+    rng = np.random.RandomState(seed)
+    dt = 2.0 ** -10
+    obs = np.zeros((n_paths, n_steps + 1), dtype=np.int64)
+    for p in range(n_paths):
+        obs[p, 1 + rng.choice(n_steps, size=min(obs_per_path, n_steps), replace=False)] = 1
+    obs[0, n_steps] = 1
+    paths = np.cumsum(rng.normal(0.0, 0.05, size=(n_paths, d, n_steps + 1)), axis=2) + 1.0
+    b = data_utils.collate_arrays(paths, obs, obs[:, 1:].sum(axis=1), dt)
+    return b, dt, n_steps * dt
+
+
+def oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=True, **kw):
+    """The oracle's hT, loss and per-parameter gradients (dropout off) in ``dtype``; inputs and
+    parameters are the fp32 values the kernels see, widened (times stay the fp32 clock's)."""
+    cast = {k: (v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in b.items()}
+    sdd = {k: v.to(dtype) for k, v in sd.items()}
+    if not grads:
+        with torch.no_grad():
+            out, _ = oracle_forward(cfg, sdd, cast, delta_t, T, **kw)
+        return out, None
+    out, params = oracle_forward(cfg, sdd, cast, delta_t, T, training=True, grads=True, **kw)
+    out[1].backward()
+    return out, {k: p.grad.detach().numpy().astype(np.float64) for k, p in params.items()}
+
+
+def kernel_names(fn):
+    """Run ``fn()`` with the library's kernel profile on; returns (fn's result, sorted kernel names)."""
+    from njode_amd import _lib
+    torch.cuda.synchronize()
+    _lib.profile_enable(1)
+    _lib.profile_read()
+    try:
+        res = fn()
+        torch.cuda.synchronize()
+        names = sorted(_lib.profile_read())
+    finally:
+        _lib.profile_enable(0)
+    return res, names
