@@ -187,8 +187,19 @@ typedef struct NjodeBatch {
  * points: shape-specialised kernels for the shapes of the build table (njode_build_info lists
  * them: the demo / PhysioNet / convergence-study shapes with widths < 64, the demo shape with
  * the GRU jump), and the shape-generic matrix-core kernels (njode_gen.h) for everything else:
- * any sizes, widths up to NJODE_GEN_MAX_WIDTH (a GRU cell: 4 x hidden_size), per-network
- * descriptions (per_net = 1), use_rnn on unmasked models. */
+ * per-network descriptions (per_net = 1), use_rnn, masked or not.  The generic kernels refuse
+ *   - input_size or output_size above 512, hidden_size above 1 024;
+ *   - masked models with input_size != output_size;
+ *   - residual_enc_dec sizes that do not divide (the reference raises there);
+ *   - more than NJODE_MAX_HIDDEN hidden layers, a layer wider than NJODE_GEN_MAX_WIDTH units
+ *     (a GRU cell: 4 x hidden_size) or with more than NJODE_GEN_MAX_WIDTH + 64 inputs (the ODE
+ *     net's first layer takes input_size + hidden_size + 2, or + 3 with input_current_t);
+ *   - shapes whose LDS images need more than 160 KB: about 2 x 16 x 4 bytes per unit of the
+ *     widest layer input plus 2 x hidden_size and 5 x max(input_size, output_size) vectors
+ *     (njode_gen.hip, build_model).  With D = 1 the first refused hidden_size is 629 for
+ *     nn_desc = None and 229 next to width-1 024 layers; unmasked D = DO at width 24 stops at
+ *     252, masked D = H = DO at width 100 at 210.
+ * On 0, njode_last_error() holds the reason. */
 #define NJODE_GEN_MAX_WIDTH 1024
 int njode_supported(const NjodeDims* dims);
 

@@ -118,7 +118,10 @@ bool build_model(const NjodeDims* d, Model& m, const char** why) {
   memset(&m, 0, sizeof(m));
   if (!d) { *why = "null dims"; return false; }
   const int D = d->input_size, H = d->hidden_size, DO = d->output_size;
-  if (D <= 0 || H <= 0 || DO <= 0 || D > 512 || H > 1024 || DO > 512) { *why = "sizes out of range"; return false; }
+  if (D <= 0 || H <= 0 || DO <= 0 || D > 512 || H > 1024 || DO > 512) {
+    *why = "sizes out of range (input_size, output_size <= 512, hidden_size <= 1024)";
+    return false;
+  }
   const bool masked = d->flags & NJODE_F_MASKED, curt = d->flags & NJODE_F_INPUT_CURRENT_T,
              res = d->flags & NJODE_F_RESIDUAL;
   // (round 5) output_size != input_size: the reference builds a readout to any output_size
@@ -154,7 +157,7 @@ bool build_model(const NjodeDims* d, Model& m, const char** why) {
   if (!build_net(a.ode, a.IN0, H, nets[0], p_off, f_off, m.pack, img_rows, max_mt, max_tb) ||
       !build_net(a.enc, masked ? 2 * D : D, H, nets[1], p_off, f_off, m.pack, img_rows, max_mt, max_tb) ||
       !build_net(a.dec, H, DO, nets[2], p_off, f_off, m.pack, img_rows, max_mt, max_tb)) {
-    *why = "network description out of range (<= 8 hidden layers, widths <= 1024, tanh / relu)";
+    *why = "network description out of range (<= 8 hidden layers, widths <= 1024, layer inputs <= 1088, tanh / relu)";
     return false;
   }
   a.rnn = (d->flags & NJODE_F_USE_RNN) ? 1 : 0;
@@ -207,7 +210,10 @@ bool build_model(const NjodeDims* d, Model& m, const char** why) {
   if (H + 4 > img_rows) img_rows = H + 4;
   a.img_rows = pad_to(img_rows + 4, 4);
   m.lds_bytes = gen_lds_floats(a.img_rows, D, H, DO) * 4;
-  if (m.lds_bytes > LDS_LIMIT) { *why = "layer images exceed the 160 KB LDS"; return false; }
+  if (m.lds_bytes > LDS_LIMIT) {
+    *why = "the LDS images (layer inputs, state, observations) exceed the 160 KB LDS of a workgroup";
+    return false;
+  }
   m.nw = max_mt < 4 ? 4 : (max_mt > 16 ? 16 : max_mt);
   if (const char* e = getenv("NJODE_GEN_NW")) {        // experiments: waves per workgroup
     const int v = atoi(e);
@@ -594,7 +600,9 @@ namespace gen {
 bool gen_supported(const NjodeDims* dims) {
   Model m;
   const char* why;
-  return build_model(dims, m, &why);
+  if (build_model(dims, m, &why)) return true;
+  fail(NJODE_E_UNSUPPORTED, "generic kernels: %s", why);   // (njode_supported leaves the reason)
+  return false;
 }
 
 size_t gen_param_count(const NjodeDims* dims) {

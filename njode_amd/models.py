@@ -524,14 +524,15 @@ class NJODE(torch.nn.Module):
                     d.nets[i].width[l] = ws[l]
                     d.nets[i].act[l] = as_[l]
         if not _lib.lib().njode_supported(ctypes.byref(d)):
+            # (njode_supported leaves the shape-generic kernels' reason in njode_last_error)
+            why = _lib.lib().njode_last_error().decode('utf-8', 'replace')
             raise NotImplementedError(
                 'libnjode_hip.so has no gfx950 kernels for input_size={}, hidden_size={}, '
                 'output_size={}, ode/enc/readout nets (n_hidden, widths, acts)={}, masked={}, '
-                'input_current_t={}, residual={}, use_rnn={} (the shape-generic kernels run '
-                'every model whose widths are <= {}; with use_rnn 4 x hidden_size too).  {}'
+                'input_current_t={}, residual={}, use_rnn={}: {}.  {}'
                 .format(self.input_size, self.hidden_size, self.output_size, self._descs,
                         self.masked, self.input_current_t, self.residual_enc_dec,
-                        self.use_rnn, 1024, _lib.build_info()))
+                        self.use_rnn, why, _lib.build_info()))
         self._dims = d
         return d
 

@@ -115,3 +115,64 @@ def kernel_names(fn):
     finally:
         _lib.profile_enable(0)
     return res, names
+
+
+def oracle_pair(cfg, sd, b, delta_t, T, predict=False, **kw):
+    """(f32, f64) oracle results of one batch: dicts of loss, hT, g (per-parameter gradients)[,
+    path_h].  ``kw['get_loss'] = False``: a prediction call (no loss, no gradients)."""
+    # (one thread: the oracle's tensors are a few paths wide, and a pool of threads only
+    # synchronises -- 0.3 s against 20 s for a 24-path batch of 100 steps on a busy host)
+    # (restored below: later tests of the session keep their own setting)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    grads = kw.get('get_loss', True)
+    try:
+        res = []
+        for dtype in (torch.float32, torch.float64):
+            out, g = oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=grads, return_path=predict, **kw)
+            r = {'hT': out[0].detach().numpy().astype(np.float64), 'g': g}
+            if grads:
+                r['loss'] = float(out[1].detach())
+            if predict:
+                r['path_h'] = out[3].detach().numpy().astype(np.float64)
+            res.append(r)
+    finally:
+        torch.set_num_threads(threads)
+    return tuple(res)
+
+
+def check_vs_oracle(tag, o32, o64, res, ratios, family, floor_h=2e-6, floor_g=1e-5, predict=False):
+    """HIP results ``res`` (loss_fused, loss_auto, hT, g.<name>, grad_fused, grad_auto[, path_h]) against
+    the float64 oracle, with the fp32 oracle's own distance from it as the yardstick:
+    err(HIP, f64) <= max(2 err(o32, f64), floor), and never looser than ATOL / RTOL / GRAD_REL_L2.  A
+    prediction call's ``res`` has no loss keys.  Records the worst ratio of ``family`` in ``ratios``."""
+    worst = 0.0
+
+    def ratio(e, e32):
+        return e / max(e32, 1e-300)
+
+    if 'loss_fused' in res:
+        l64 = o64['loss']
+        e32 = abs(o32['loss'] - l64)
+        for key in ('loss_fused', 'loss_auto'):
+            e = abs(res[key] - l64)
+            assert e <= max(2 * e32, 1e-6 * abs(l64)), (tag, key, res[key], l64, e, e32)
+            assert e <= 1e-4 * abs(l64), (tag, key)
+    eh, eh32 = np.abs(res['hT'] - o64['hT']).max(), np.abs(o32['hT'] - o64['hT']).max()
+    assert eh <= max(2 * eh32, floor_h), (tag, 'hT', eh, eh32)
+    np.testing.assert_allclose(res['hT'], o64['hT'], atol=ATOL, rtol=RTOL, err_msg=tag)
+    worst = max(worst, ratio(eh, eh32))
+    if 'loss_fused' in res:
+        for k in o64['g']:
+            e, e32g = rel_l2(res['g.' + k], o64['g'][k]), rel_l2(o32['g'][k], o64['g'][k])
+            assert e <= max(2 * e32g, floor_g), (tag, k, e, e32g)
+            assert e <= GRAD_REL_L2, (tag, k, e)
+            worst = max(worst, ratio(e, e32g))
+        # the fused step: the same kernels, the same numbers (flat, in the model's parameter order)
+        assert rel_l2(res['grad_fused'], res['grad_auto']) < 1e-5, (tag, rel_l2(res['grad_fused'], res['grad_auto']))
+    if predict:
+        ep, ep32 = np.abs(res['path_h'] - o64['path_h']).max(), np.abs(o32['path_h'] - o64['path_h']).max()
+        assert ep <= max(2 * ep32, floor_h), (tag, 'path_h', ep, ep32)
+        worst = max(worst, ratio(ep, ep32))
+    ratios[family] = max(ratios.get(family, 0.0), worst)
+    print('{:40s} worst err(HIP, f64) / err(o32, f64) = {:.2f}'.format(tag, worst))

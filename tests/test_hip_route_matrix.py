@@ -33,8 +33,8 @@ import numpy as np
 import pytest
 import torch
 
-from hip_util import (ATOL, GRAD_REL_L2, RTOL, bs_batch, exact_k_batch, hip_model, kernel_names,
-                      oracle_truth, rel_l2)
+import hip_util
+from hip_util import bs_batch, exact_k_batch, hip_model, kernel_names, oracle_pair, rel_l2
 from njode_amd.build import CONFIGS, RELU
 
 pytestmark = pytest.mark.gpu
@@ -238,26 +238,11 @@ def truth(c, kind, predict=False):
     """(f32, f64) oracle results of configuration c on batch kind: dicts of loss, hT, grads[, path_h]."""
     key = (tuple(c), kind)
     if key not in _ORACLE or (predict and 'path_h' not in _ORACLE[key][1]):
-        # (one thread: the oracle's tensors are a few paths wide, and a pool of threads only
-        # synchronises -- 0.3 s against 20 s for a 24-path batch of 100 steps on a busy host)
-        # (restored below: later tests of the session keep their own setting)
-        threads = torch.get_num_threads()
-        torch.set_num_threads(1)
-        try:
-            from njode_amd import models
-            torch.manual_seed(0)
-            sd = {k: v.detach().clone() for k, v in models.NJODE(**model_cfg(c)).state_dict().items()}
-            b, dt, T = make_batch(kind, c)
-            res = []
-            for dtype in (torch.float32, torch.float64):
-                out, g = oracle_truth(model_cfg(c), sd, b, dt, T, dtype, return_path=predict)
-                r = {'loss': float(out[1].detach()), 'hT': out[0].detach().numpy().astype(np.float64), 'g': g}
-                if predict:
-                    r['path_h'] = out[3].detach().numpy().astype(np.float64)
-                res.append(r)
-        finally:
-            torch.set_num_threads(threads)
-        _ORACLE[key] = tuple(res)
+        from njode_amd import models
+        torch.manual_seed(0)
+        sd = {k: v.detach().clone() for k, v in models.NJODE(**model_cfg(c)).state_dict().items()}
+        b, dt, T = make_batch(kind, c)
+        _ORACLE[key] = oracle_pair(model_cfg(c), sd, b, dt, T, predict=predict)
     return _ORACLE[key]
 
 
@@ -266,34 +251,7 @@ RATIOS = {}
 
 def check_vs_oracle(tag, family, c, kind, res, floor_h=2e-6, floor_g=1e-5, predict=False):
     o32, o64 = truth(c, kind, predict)
-    worst = 0.0
-
-    def ratio(e, e32):
-        return e / max(e32, 1e-300)
-
-    l64 = o64['loss']
-    e32 = abs(o32['loss'] - l64)
-    for key in ('loss_fused', 'loss_auto'):
-        e = abs(res[key] - l64)
-        assert e <= max(2 * e32, 1e-6 * abs(l64)), (tag, key, res[key], l64, e, e32)
-        assert e <= 1e-4 * abs(l64), (tag, key)
-    eh, eh32 = np.abs(res['hT'] - o64['hT']).max(), np.abs(o32['hT'] - o64['hT']).max()
-    assert eh <= max(2 * eh32, floor_h), (tag, 'hT', eh, eh32)
-    np.testing.assert_allclose(res['hT'], o64['hT'], atol=ATOL, rtol=RTOL, err_msg=tag)
-    worst = max(worst, ratio(eh, eh32))
-    for k in o64['g']:
-        e, e32g = rel_l2(res['g.' + k], o64['g'][k]), rel_l2(o32['g'][k], o64['g'][k])
-        assert e <= max(2 * e32g, floor_g), (tag, k, e, e32g)
-        assert e <= GRAD_REL_L2, (tag, k, e)
-        worst = max(worst, ratio(e, e32g))
-    # the fused step: the same kernels, the same numbers (flat, in the model's parameter order)
-    assert rel_l2(res['grad_fused'], res['grad_auto']) < 1e-5, (tag, rel_l2(res['grad_fused'], res['grad_auto']))
-    if predict:
-        ep, ep32 = np.abs(res['path_h'] - o64['path_h']).max(), np.abs(o32['path_h'] - o64['path_h']).max()
-        assert ep <= max(2 * ep32, floor_h), (tag, 'path_h', ep, ep32)
-        worst = max(worst, ratio(ep, ep32))
-    RATIOS[family] = max(RATIOS.get(family, 0.0), worst)
-    print('{:40s} worst err(HIP, f64) / err(o32, f64) = {:.2f}'.format(tag, worst))
+    hip_util.check_vs_oracle(tag, o32, o64, res, RATIOS, family, floor_h, floor_g, predict)
 
 
 def has(names, want):

@@ -274,6 +274,149 @@ def test_library_loads_and_exports_declared_symbols():
     assert b'use_rnn' in L.njode_last_error()
 
 
+def _envelope_grid():
+    """Deterministic grid of (D, H, DO, nets, flags) around every bound of build_model: coarse
+    sweeps of one size per family and flag combination, step 1 next to the first refused value the
+    restatement finds, and the size / residual / depth / width / activation edges."""
+    from gen_envelope import restate
+    T, R = _lib.ACT_TANH, _lib.ACT_RELU
+    grid = []
+
+    def uni(n, w, act=T):
+        return (n, (w,) * n, (act,) * n)
+
+    def sweep(fam, lo, hi, flag_sets):
+        for flags in flag_sets:
+            first = next((x for x in range(lo, hi + 1) if restate(*fam(x), flags)[0] is not None), None)
+            xs = set(range(lo, hi + 1, 37)) | {lo, hi}
+            if first is not None:
+                xs |= set(range(max(lo, first - 3), min(hi, first + 3) + 1))
+            grid.extend(fam(x) + (flags,) for x in sorted(xs))
+
+    every = range(32)
+    unmasked = [f for f in every if not f & _lib.F_MASKED]
+    sweep(lambda h: (1, h, 1, uni(0, 0)), 1, 1030, every)                       # nn_desc = None
+    sweep(lambda h: (1, h, 1, uni(2, 50)), 1, 1030, every)                      # width 50 (use_rnn: 4H)
+    sweep(lambda h: (1, h, 1, uni(2, 1024, R)), 1, 300, (0, 1, 2, 16, 17))      # width 1 024
+    sweep(lambda d: (d, 10, d, uni(2, 24)), 1, 520, unmasked)                  # unmasked D = DO
+    sweep(lambda d: (d, d, d, uni(2, 100)), 1, 520, [f for f in every if f & _lib.F_MASKED])   # masked D = H = DO
+    sweep(lambda w: (1, 10, 1, uni(1, w)), 1, 1100, (0, 16))                   # widths
+    sweep(lambda w: (2, 6, 2, uni(8, w, R)), 1, 1100, (4, 5))
+    sweep(lambda w: (3, 7, 3, ((1, (w,), (T,)), (0, (), ()), (2, (40, 40), (T, R)))), 1, 1100, (0, 1))
+    # sizes
+    for D in (-1, 0, 1, 511, 512, 513):
+        for H in (0, 1, 1023, 1024, 1025):
+            for DO in (0, 1, 512, 513):
+                grid.append((D, H, DO, uni(0, 0), 0))
+    # residual cases and output_size != input_size
+    for D in (1, 2, 3, 4, 6, 8, 12):
+        for H in (1, 2, 3, 4, 6, 8, 12):
+            for DO in (1, 2, 3, 4, 6, 8, 12):
+                for flags in (4, 5, 0, 1):
+                    grid.append((D, H, DO, uni(1, 20), flags))
+    # depth, per-network descriptions, activations, bad widths
+    for n in (-1, 0, 1, 4, 8, 9, 10):
+        for flags in (0, 4, 16):
+            grid.append((2, 4, 2, (n, (33,) * max(n, 0), (R,) * max(n, 0)), flags))
+    for n0 in (0, 1, 8, 9):
+        for n1 in (0, 3, 8):
+            for n2 in (0, 2, 8, 9):
+                ws = lambda n, b: tuple(b + 13 * l for l in range(n))
+                acts = lambda n: tuple((T, R)[l % 2] for l in range(n))
+                grid.append((3, 6, 3, ((n0, ws(n0, 17), acts(n0)), (n1, ws(n1, 64), acts(n1)),
+                                       (n2, ws(n2, 127), acts(n2))), 4))
+    for bad in ((2, (50, 0), (T, T)), (2, (50, -4), (T, T)), (2, (50, 50), (T, 2)), (2, (50, 50), (-1, T)),
+                (1, (1024,), (T,)), (1, (1025,), (T,))):
+        grid.append((1, 10, 1, (bad, (0, (), ()), (0, (), ())), 0))
+        grid.append((1, 10, 1, ((0, (), ()), (0, (), ()), bad), 0))
+    return grid
+
+
+def _param_count_of_torch_model(D, H, DO, nets, flags):
+    """Parameters of models.NJODE built on the meta device (no memory): the flat vector's length."""
+    if not (len(nets) == 3 and isinstance(nets[0], tuple)):
+        nets = (nets, nets, nets)
+
+    def desc(n, ws, acts):
+        return None if n == 0 else tuple((ws[l], 'tanh' if acts[l] == _lib.ACT_TANH else 'relu') for l in range(n))
+    opts = {'masked': bool(flags & _lib.F_MASKED), 'input_current_t': bool(flags & _lib.F_INPUT_CURRENT_T),
+            'residual_enc_dec': bool(flags & _lib.F_RESIDUAL),
+            'which_loss': 'easy' if flags & _lib.F_LOSS_EASY else 'standard'}
+    with torch.device('meta'):
+        m = models.NJODE(D, H, DO, desc(*nets[0]), desc(*nets[2]), desc(*nets[1]),
+                         use_rnn=bool(flags & _lib.F_USE_RNN), bias=True, dropout_rate=0.0, options=opts)
+    return sum(p.numel() for p in m.parameters())
+
+
+def test_generic_envelope_restatement_matches_the_library(capsys):
+    """njode_supported agrees EXACTLY with a Python restatement of build_model (tests/gen_envelope.py)
+    over a grid around every bound; njode_param_count with the torch model's parameter count; every
+    refusal leaves its reason in njode_last_error, and NJODE._get_dims quotes it."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip('libnjode_hip.so not built in this checkout (run __graft_entry__.build())')
+    import contextlib
+    import io
+    from gen_envelope import (R_LDS, R_MASKED, R_NET, R_NHIDDEN, R_RESIDUAL, R_RNN, R_SIZES, XR, dims_of,
+                              restate)
+    L = _lib.lib()
+    grid = _envelope_grid()
+    assert len(grid) >= 2000, len(grid)
+    n_ok, reasons, mismatch = 0, {}, []
+    for D, H, DO, nets, flags in grid:
+        d = dims_of(D, H, DO, nets, flags)
+        why, model = restate(D, H, DO, nets, flags)
+        got = L.njode_supported(ctypes.byref(d))
+        if got != (why is None):
+            mismatch.append(((D, H, DO, nets, flags), why, got, L.njode_last_error()))
+            continue
+        if why is None:
+            n_ok += 1
+            P = L.njode_param_count(ctypes.byref(d))
+            assert P == model['P'], ((D, H, DO, nets, flags), P, model['P'])
+            with contextlib.redirect_stdout(io.StringIO()):   # (the model prints its loss name)
+                assert P == _param_count_of_torch_model(D, H, DO, nets, flags), (D, H, DO, nets, flags)
+            # at the default waves per workgroup every admitted shape holds its observations in
+            # registers (k_gen_fwd's other branch runs only under NJODE_GEN_NW)
+            assert D * 16 <= XR * 64 * model['nw'], (D, H, DO, nets, flags, model['nw'])
+        else:
+            err = L.njode_last_error().decode()
+            assert err.startswith('generic kernels: ') and why in err, ((D, H, DO, nets, flags), why, err)
+            assert L.njode_param_count(ctypes.byref(d)) == 0
+            reasons[why] = reasons.get(why, 0) + 1
+    assert not mismatch, mismatch[:10]
+    assert set(reasons) >= {R_SIZES, R_MASKED, R_RESIDUAL, R_NHIDDEN, R_NET, R_RNN, R_LDS}, reasons
+    # the first refused sizes of the documented families (include/njode_hip.h, DESIGN section 1)
+    T = _lib.ACT_TANH
+
+    def first(fam, flags=0):
+        return next(x for x in range(1, 1100) if restate(*fam(x), flags)[0] is not None)
+    assert first(lambda h: (1, h, 1, (0, (), ()))) == 629
+    assert first(lambda h: (1, h, 1, (2, (50, 50), (T, T))), _lib.F_USE_RNN) == 253
+    assert first(lambda h: (1, h, 1, (2, (1024, 1024), (T, T)))) == 229
+    assert first(lambda d: (d, 10, d, (2, (24, 24), (T, T)))) == 252
+    assert first(lambda d: (d, d, d, (2, (100, 100), (T, T))), _lib.F_MASKED) == 210
+    # NJODE._get_dims names the library's reason
+    nn50 = ((50, 'tanh'), (50, 'tanh'))
+    for kw, why in ((dict(input_size=513, hidden_size=10, output_size=513), R_SIZES),
+                    (dict(input_size=3, hidden_size=6, output_size=12, options={'masked': True, 'residual_enc_dec': False}),
+                     R_MASKED),
+                    (dict(ode_nn=((1025, 'tanh'),)), R_NET),
+                    (dict(ode_nn=((20, 'tanh'),) * 9, enc_nn=((20, 'tanh'),) * 9, readout_nn=((20, 'tanh'),) * 9),
+                     R_NHIDDEN),
+                    (dict(hidden_size=257, use_rnn=True), R_RNN),
+                    (dict(hidden_size=629, ode_nn=None, enc_nn=None, readout_nn=None), R_LDS)):
+        cfg = dict(input_size=1, hidden_size=10, output_size=1, ode_nn=nn50, readout_nn=nn50, enc_nn=nn50,
+                   use_rnn=False, bias=True, dropout_rate=0.0, options={'residual_enc_dec': False})
+        cfg.update(kw)
+        with contextlib.redirect_stdout(io.StringIO()), torch.device('meta'):
+            m = models.NJODE(**cfg)
+        with pytest.raises(NotImplementedError) as e:
+            m._get_dims()
+        assert 'generic kernels: ' in str(e.value) and why in str(e.value), (kw, str(e.value))
+    with capsys.disabled():
+        print('\n[envelope] {} grid dims checked: {} accepted, refused {}'.format(len(grid), n_ok, reasons))
+
+
 def test_torch_library_operator_is_registered_with_a_fake_implementation():
     """njode_amd/ops.py: torch.ops.njode_amd.forward exists (dispatcher-visible operator) and its
     fake implementation gives the output shapes without touching a GPU."""
