@@ -23,6 +23,13 @@ What each function follows (reference file:line):
 * ``paper_loss``                -- ``models.py:71-126`` (compute_loss / _2)
 * ``euler_clock``               -- ``models.py:430-439, 497-505`` (float64 clock)
 * ``OracleNJODE.forward``       -- ``models.py:379-518``
+
+Dropout: by default ``F.dropout`` (torch's masks, for the statistical tests).  A mask source
+(``OracleNJODE.masks``, e.g. ``oracle.dropout_oracle.KernelMasks``) replaces it with the masks a
+kernel family draws: every network evaluation is keyed by (net id, time key, batch rows) and each
+hidden layer is multiplied by keep * the kernels' fp32 scale.  With a mask source, a path-output
+row of a jump keeps, for the paths the jump does not touch, their previous row's readout (what
+the kernels write; in eval mode the two are the same numbers).
 """
 import math
 
@@ -31,6 +38,9 @@ import torch
 import torch.nn.functional as F
 
 EPS = 1e-10
+# network ids and time keys of the kernels' dropout streams (njode_kernels.h:14-15)
+NET_ODE, NET_ENC, NET_DEC, NET_DEC_BJ, NET_DEC_ROW = 0, 1, 2, 3, 4
+TKEY_START = 0xFFFFFFFF
 
 
 def layer_sizes(in_size, out_size, nn_desc):
@@ -72,14 +82,16 @@ class OracleNet:
                 out['{}.{}.bias'.format(self.prefix, 3 * k)] = (o,)
         return out
 
-    def __call__(self, params, x, p_drop, training):
-        for k, (_, _, act) in enumerate(self.layers):
+    def __call__(self, params, x, p_drop, training, drop=None):
+        """``drop``: None (``F.dropout``) or ``drop(layer, width)`` -> the multiplier (keep * scale,
+        [rows, width], x's dtype) of hidden layer ``layer``."""
+        for k, (_, width, act) in enumerate(self.layers):
             w = params['{}.{}.weight'.format(self.prefix, 3 * k)]
             b = params.get('{}.{}.bias'.format(self.prefix, 3 * k))
             x = F.linear(x, w, b)
             if act is not None:
                 x = torch.tanh(x) if act == 'tanh' else torch.relu(x)
-                x = F.dropout(x, p_drop, training)
+                x = F.dropout(x, p_drop, training) if drop is None else x * drop(k, width)
         return x
 
 
@@ -131,6 +143,7 @@ class OracleNJODE:
         self.use_rnn = use_rnn
         self.bias = bias
         self.training = False
+        self.masks = None      # mask source: see the module docstring
         extra = 3 if input_current_t else 2
         self.ode = OracleNet('ode_f.f', input_size + hidden_size + extra,
                              hidden_size, ode_nn, bias)
@@ -190,11 +203,23 @@ class OracleNJODE:
         return params
 
     # -- sub-maps ---------------------------------------------------------------
-    def ffnn(self, net, res, params, x, mask=None):
+    def _drop(self, key, dtype):
+        """The ``drop`` callable of one network evaluation ``key = (net, tkey, rows)``, or None."""
+        if key is None or self.masks is None or not self.training:
+            return None
+        net, tkey, rows = key
+        scale = self.masks.scale
+
+        def drop(layer, width):
+            keep = torch.from_numpy(self.masks(net, tkey, rows, layer, width).astype(np.float64))
+            return (keep * scale).to(dtype)
+        return drop
+
+    def ffnn(self, net, res, params, x, mask=None, key=None):
         inp = torch.tanh(x)
         if mask is not None:
             inp = torch.cat((inp, mask), 1)
-        out = net(params, inp, self.p_drop, self.training)
+        out = net(params, inp, self.p_drop, self.training, self._drop(key, x.dtype))
         case, mult = res
         if case == 1:
             return x.repeat(1, mult) + out
@@ -202,18 +227,18 @@ class OracleNJODE:
             return torch.mean(torch.stack(x.chunk(mult, dim=1)), dim=0) + out
         return out
 
-    def encode(self, params, x, mask=None):
-        return self.ffnn(self.enc, self.enc_res, params, x, mask)
+    def encode(self, params, x, mask=None, key=None):
+        return self.ffnn(self.enc, self.enc_res, params, x, mask, key)
 
-    def readout(self, params, h):
-        return self.ffnn(self.dec, self.dec_res, params, h)
+    def readout(self, params, h, key=None):
+        return self.ffnn(self.dec, self.dec_res, params, h, key=key)
 
-    def ode_rhs(self, params, x, h, tau, tdiff):
+    def ode_rhs(self, params, x, h, tau, tdiff, key=None):
         parts = [torch.tanh(x), torch.tanh(h), tau, tdiff]
         if self.input_current_t:
             parts.append(tau + tdiff)
         return self.ode(params, torch.cat(parts, dim=1), self.p_drop,
-                        self.training)
+                        self.training, self._drop(key, h.dtype))
 
     def gru_jump(self, params, h, X_obs, i_obs):
         gi = F.linear(torch.tanh(X_obs), params['obs_c.gru_d.weight_ih'],
@@ -236,31 +261,38 @@ class OracleNJODE:
                 n_obs_ot, return_path=False, get_loss=True, until_T=False,
                 M=None):
         B = start_X.shape[0]
+        # mask keys (net, time key, batch rows): oracle/dropout_oracle.py, njode_kernels.h:14-15
+        every = np.arange(B)
+        start_key = (NET_ENC, TKEY_START, every)
         if self.masked:
-            h = self.encode(params, start_X, torch.zeros_like(start_X))
+            h = self.encode(params, start_X, torch.zeros_like(start_X), key=start_key)
         else:
-            h = self.encode(params, start_X)
+            h = self.encode(params, start_X, key=start_key)
         last_X = start_X
         tau = torch.zeros(B, 1)
         now = 0.0
         loss = 0
         rec_t, rec_h, rec_y = [], [], []
 
-        def record(t, h_):
+        def record(t, h_, tkey):
             if return_path:
                 rec_t.append(t)
                 rec_h.append(h_)
-                rec_y.append(self.readout(params, h_))
+                rec_y.append(self.readout(params, h_, key=(NET_DEC_ROW, tkey, every)))
 
-        record(0, h)
+        record(0, h, TKEY_START - 1)
+        n_steps = [0]      # Euler steps taken: the time key of the ODE net and of the jumps
         assert len(times) + 1 == len(time_ptr)
 
         def evolve(h_, now_, target):
             for step, t0 in euler_clock(now_, target, delta_t):
+                k = n_steps[0]
                 # python-float minus fp32 tensor: ATen casts the scalar to fp32
-                h_ = h_ + step * self.ode_rhs(params, last_X, h_, tau, t0 - tau)
+                h_ = h_ + step * self.ode_rhs(params, last_X, h_, tau, t0 - tau,
+                                              key=(NET_ODE, k, every))
                 now_ = t0 + step
-                record(now_, h_)
+                n_steps[0] = k + 1
+                record(now_, h_, 0x80000000 + k)
             return h_, now_
 
         for i, obs_time in enumerate(times):
@@ -269,19 +301,21 @@ class OracleNJODE:
             X_obs = X[lo:hi]
             i_obs = obs_idx[lo:hi]
             M_obs = M[lo:hi] if self.masked else None
+            kj = n_steps[0]
+            rows = i_obs.numpy()
 
-            Y_bj = self.readout(params, h)
+            Y_bj = self.readout(params, h, key=(NET_DEC_BJ, kj, every))
             if self.use_rnn:
                 h = self.gru_jump(params, h, X_obs, i_obs)
             else:
                 if self.masked:
                     x_in = X_obs * M_obs + (1 - M_obs) * Y_bj[i_obs]
-                    new = self.encode(params, x_in, M_obs)
+                    new = self.encode(params, x_in, M_obs, key=(NET_ENC, kj, rows))
                 else:
-                    new = self.encode(params, X_obs)
+                    new = self.encode(params, X_obs, key=(NET_ENC, kj, rows))
                 h = h.clone()
                 h[i_obs] = new
-            Y = self.readout(params, h)
+            Y = self.readout(params, h, key=(NET_DEC, kj, every))
 
             if get_loss:
                 loss = loss + paper_loss(
@@ -295,7 +329,13 @@ class OracleNJODE:
             if return_path:
                 rec_t.append(obs_time)
                 rec_h.append(h)
-                rec_y.append(Y)
+                if self.masks is not None and self.training:
+                    # (the kernels keep an untouched path's previous readout; see the docstring)
+                    Y_row = rec_y[-1].clone()
+                    Y_row[i_obs] = Y[i_obs]
+                    rec_y.append(Y_row)
+                else:
+                    rec_y.append(Y)
 
         if until_T:
             h, now = evolve(h, now, T)

@@ -45,9 +45,10 @@ def hip_forward(m, b, delta_t, T, **kw):
              d.get('n_obs_ot'), M=d.get('M'), **kw)
 
 
-def oracle_forward(cfg, sd, b, delta_t, T, training=False, weight=None, grads=False, **kw):
+def oracle_forward(cfg, sd, b, delta_t, T, training=False, weight=None, grads=False, masks=None, **kw):
     o = njode_oracle.make_oracle(cfg)
     o.training = training
+    o.masks = masks
     if weight is not None:
         o.weight = weight
     params = {k: v.clone().requires_grad_(grads) for k, v in sd.items()}
@@ -88,17 +89,20 @@ def exact_k_batch(n_paths, n_steps, obs_per_path=4, seed=0, d=1):
     return b, dt, n_steps * dt
 
 
-def oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=True, **kw):
-    """The oracle's hT, loss and per-parameter gradients (dropout off) in ``dtype``; inputs and
-    parameters are the fp32 values the kernels see, widened (times stay the fp32 clock's)."""
+def oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=True, masks=None, c_hT=None, **kw):
+    """The oracle's hT, loss and per-parameter gradients in ``dtype``; inputs and parameters are the
+    fp32 values the kernels see, widened (times stay the fp32 clock's).  Dropout is off, or, with
+    ``masks`` (a mask source, oracle/dropout_oracle.KernelMasks), the kernels' masks in a training
+    call.  ``c_hT``: the gradients are those of loss + (c_hT hT).sum()."""
     cast = {k: (v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in b.items()}
     sdd = {k: v.to(dtype) for k, v in sd.items()}
     if not grads:
         with torch.no_grad():
-            out, _ = oracle_forward(cfg, sdd, cast, delta_t, T, **kw)
+            out, _ = oracle_forward(cfg, sdd, cast, delta_t, T, training=masks is not None, masks=masks, **kw)
         return out, None
-    out, params = oracle_forward(cfg, sdd, cast, delta_t, T, training=True, grads=True, **kw)
-    out[1].backward()
+    out, params = oracle_forward(cfg, sdd, cast, delta_t, T, training=True, grads=True, masks=masks, **kw)
+    obj = out[1] if c_hT is None else out[1] + (torch.as_tensor(c_hT).to(dtype) * out[0]).sum()
+    obj.backward()
     return out, {k: p.grad.detach().numpy().astype(np.float64) for k, p in params.items()}
 
 
@@ -117,9 +121,12 @@ def kernel_names(fn):
     return res, names
 
 
-def oracle_pair(cfg, sd, b, delta_t, T, predict=False, **kw):
+def oracle_pair(cfg, sd, b, delta_t, T, predict=False, masks=None, **kw):
     """(f32, f64) oracle results of one batch: dicts of loss, hT, g (per-parameter gradients)[,
-    path_h].  ``kw['get_loss'] = False``: a prediction call (no loss, no gradients)."""
+    path_h, path_y].  ``kw['get_loss'] = False``: a prediction call (no loss, no gradients).
+    ``masks``: a mask source (oracle/dropout_oracle.KernelMasks): a training call with the
+    kernels' own dropout masks, the same masks in fp32 and float64 (``check_vs_oracle``'s
+    yardstick stays the fp32 oracle's distance from float64)."""
     # (one thread: the oracle's tensors are a few paths wide, and a pool of threads only
     # synchronises -- 0.3 s against 20 s for a 24-path batch of 100 steps on a busy host)
     # (restored below: later tests of the session keep their own setting)
@@ -129,12 +136,14 @@ def oracle_pair(cfg, sd, b, delta_t, T, predict=False, **kw):
     try:
         res = []
         for dtype in (torch.float32, torch.float64):
-            out, g = oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=grads, return_path=predict, **kw)
+            out, g = oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=grads, masks=masks, return_path=predict,
+                                  **kw)
             r = {'hT': out[0].detach().numpy().astype(np.float64), 'g': g}
             if grads:
                 r['loss'] = float(out[1].detach())
             if predict:
                 r['path_h'] = out[3].detach().numpy().astype(np.float64)
+                r['path_y'] = out[4].detach().numpy().astype(np.float64)
             res.append(r)
     finally:
         torch.set_num_threads(threads)
@@ -142,7 +151,7 @@ def oracle_pair(cfg, sd, b, delta_t, T, predict=False, **kw):
 
 
 def check_vs_oracle(tag, o32, o64, res, ratios, family, floor_h=2e-6, floor_g=1e-5, predict=False):
-    """HIP results ``res`` (loss_fused, loss_auto, hT, g.<name>, grad_fused, grad_auto[, path_h]) against
+    """HIP results ``res`` (loss_fused, loss_auto, hT, g.<name>, grad_fused, grad_auto[, path_h, path_y]) against
     the float64 oracle, with the fp32 oracle's own distance from it as the yardstick:
     err(HIP, f64) <= max(2 err(o32, f64), floor), and never looser than ATOL / RTOL / GRAD_REL_L2.  A
     prediction call's ``res`` has no loss keys.  Records the worst ratio of ``family`` in ``ratios``."""
@@ -174,5 +183,9 @@ def check_vs_oracle(tag, o32, o64, res, ratios, family, floor_h=2e-6, floor_g=1e
         ep, ep32 = np.abs(res['path_h'] - o64['path_h']).max(), np.abs(o32['path_h'] - o64['path_h']).max()
         assert ep <= max(2 * ep32, floor_h), (tag, 'path_h', ep, ep32)
         worst = max(worst, ratio(ep, ep32))
+        if 'path_y' in res:
+            ey, ey32 = np.abs(res['path_y'] - o64['path_y']).max(), np.abs(o32['path_y'] - o64['path_y']).max()
+            assert ey <= max(2 * ey32, floor_h), (tag, 'path_y', ey, ey32)
+            worst = max(worst, ratio(ey, ey32))
     ratios[family] = max(ratios.get(family, 0.0), worst)
     print('{:40s} worst err(HIP, f64) / err(o32, f64) = {:.2f}'.format(tag, worst))
