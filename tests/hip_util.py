@@ -89,6 +89,51 @@ def exact_k_batch(n_paths, n_steps, obs_per_path=4, seed=0, d=1):
     return b, dt, n_steps * dt
 
 
+def irregular_batch(b, dt, dt_factor=0.37):
+    """(batch, delta_t): ``b`` (a collated batch of grid step ``dt``) made irregular, a pure function of
+    its arguments.  Every row of one path -- not path 0, not a path of the last observed slice -- is
+    removed (``n_obs_ot`` recounted, slices it leaves empty stay); a jump at t = 0.0 with one row for
+    path 0 is put in front (no Euler step before it; kept if the batch already has it); a time without
+    rows is inserted midway between two inner times; delta_t = dt_factor dt does not divide the grid,
+    so every grid interval ends in a partial Euler step."""
+    times = np.asarray(b['times'], dtype=np.float64)
+    ptr = np.asarray(b['time_ptr'], dtype=np.int64)
+    idx = b['obs_idx'].numpy()
+    B, d = b['start_X'].shape[0], b['X'].shape[1]
+    assert len(times) >= 3 and ptr[-1] == len(idx) > 0
+    slice_of = np.repeat(np.arange(len(times)), np.diff(ptr))
+    last = set(idx[slice_of == slice_of[-1]].tolist())
+    seen = set(idx.tolist())
+    victim = next(p for p in range(1, B) if p in seen and p not in last)
+    keep = idx != victim
+    idx2, sl2 = idx[keep], slice_of[keep]
+    kt = torch.from_numpy(keep)
+    X, M = b['X'][kt], (b['M'][kt] if 'M' in b else None)
+    counts = np.bincount(sl2, minlength=len(times))
+    # the t = 0 jump of path 0 (rows are sorted by time, then path: it is row 0)
+    if times[0] != 0.0 or not (counts[0] and idx2[0] == 0):
+        m0 = (torch.arange(d) % 3 == 0).to(X.dtype)
+        x0 = 0.5 + 0.01 * torch.arange(d, dtype=X.dtype)
+        if M is not None:
+            x0, M = x0 * m0, torch.cat([m0[None], M])
+        X, idx2 = torch.cat([x0[None], X]), np.concatenate([[0], idx2])
+        if times[0] != 0.0:
+            times, counts = np.concatenate([[0.0], times]), np.concatenate([[1], counts])
+        else:
+            counts[0] += 1
+    # a time without rows, strictly inside the range and off the grid
+    j = len(times) // 2
+    times = np.insert(times, j + 1, 0.5 * (times[j] + times[j + 1]))
+    counts = np.insert(counts, j + 1, 0)
+    out = {k: v for k, v in b.items() if k not in ('true_paths', 'observed_dates')}
+    out.update(times=times, time_ptr=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), X=X,
+               obs_idx=torch.tensor(idx2, dtype=torch.long),
+               n_obs_ot=torch.tensor(np.bincount(idx2, minlength=B).astype(np.int64)))
+    if M is not None:
+        out['M'] = M
+    return out, dt_factor * dt
+
+
 def oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=True, masks=None, c_hT=None, **kw):
     """The oracle's hT, loss and per-parameter gradients in ``dtype``; inputs and parameters are the
     fp32 values the kernels see, widened (times stay the fp32 clock's).  Dropout is off, or, with
@@ -121,9 +166,10 @@ def kernel_names(fn):
     return res, names
 
 
-def oracle_pair(cfg, sd, b, delta_t, T, predict=False, masks=None, **kw):
+def oracle_pair(cfg, sd, b, delta_t, T, predict=False, masks=None, grads=None, **kw):
     """(f32, f64) oracle results of one batch: dicts of loss, hT, g (per-parameter gradients)[,
-    path_h, path_y].  ``kw['get_loss'] = False``: a prediction call (no loss, no gradients).
+    path_h, path_y].  ``kw['get_loss'] = False``: a prediction call (no loss, no gradients);
+    ``grads=False``: an eval-mode call that keeps its loss (no gradients).
     ``masks``: a mask source (oracle/dropout_oracle.KernelMasks): a training call with the
     kernels' own dropout masks, the same masks in fp32 and float64 (``check_vs_oracle``'s
     yardstick stays the fp32 oracle's distance from float64)."""
@@ -132,14 +178,15 @@ def oracle_pair(cfg, sd, b, delta_t, T, predict=False, masks=None, **kw):
     # (restored below: later tests of the session keep their own setting)
     threads = torch.get_num_threads()
     torch.set_num_threads(1)
-    grads = kw.get('get_loss', True)
+    get_loss = kw.get('get_loss', True)
+    grads = get_loss if grads is None else grads
     try:
         res = []
         for dtype in (torch.float32, torch.float64):
             out, g = oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=grads, masks=masks, return_path=predict,
                                   **kw)
             r = {'hT': out[0].detach().numpy().astype(np.float64), 'g': g}
-            if grads:
+            if get_loss:
                 r['loss'] = float(out[1].detach())
             if predict:
                 r['path_h'] = out[3].detach().numpy().astype(np.float64)
@@ -154,38 +201,46 @@ def check_vs_oracle(tag, o32, o64, res, ratios, family, floor_h=2e-6, floor_g=1e
     """HIP results ``res`` (loss_fused, loss_auto, hT, g.<name>, grad_fused, grad_auto[, path_h, path_y]) against
     the float64 oracle, with the fp32 oracle's own distance from it as the yardstick:
     err(HIP, f64) <= max(2 err(o32, f64), floor), and never looser than ATOL / RTOL / GRAD_REL_L2.  A
-    prediction call's ``res`` has no loss keys.  Records the worst ratio of ``family`` in ``ratios``."""
-    worst = 0.0
+    prediction call's ``res`` has no loss keys, or ``loss_predict`` alone (``get_loss=True``: no
+    gradients); a step the fused call cannot make (``until_T``) has no ``loss_fused`` / ``grad_fused``.
+    Records the worst ratio of ``family`` in ``ratios``."""
+    worst, worst_of = 0.0, ('', 0.0, 0.0)
 
-    def ratio(e, e32):
-        return e / max(e32, 1e-300)
+    def ratio(e, e32, what=''):
+        nonlocal worst, worst_of
+        r = e / max(e32, 1e-300)
+        if r > worst:
+            worst, worst_of = r, (what, e, e32)
+        return r
 
-    if 'loss_fused' in res:
+    loss_keys = [k for k in ('loss_fused', 'loss_auto', 'loss_predict') if k in res]
+    if loss_keys:
         l64 = o64['loss']
         e32 = abs(o32['loss'] - l64)
-        for key in ('loss_fused', 'loss_auto'):
+        for key in loss_keys:
             e = abs(res[key] - l64)
             assert e <= max(2 * e32, 1e-6 * abs(l64)), (tag, key, res[key], l64, e, e32)
             assert e <= 1e-4 * abs(l64), (tag, key)
     eh, eh32 = np.abs(res['hT'] - o64['hT']).max(), np.abs(o32['hT'] - o64['hT']).max()
     assert eh <= max(2 * eh32, floor_h), (tag, 'hT', eh, eh32)
     np.testing.assert_allclose(res['hT'], o64['hT'], atol=ATOL, rtol=RTOL, err_msg=tag)
-    worst = max(worst, ratio(eh, eh32))
-    if 'loss_fused' in res:
+    ratio(eh, eh32, 'hT')
+    if 'loss_auto' in res:
         for k in o64['g']:
             e, e32g = rel_l2(res['g.' + k], o64['g'][k]), rel_l2(o32['g'][k], o64['g'][k])
             assert e <= max(2 * e32g, floor_g), (tag, k, e, e32g)
             assert e <= GRAD_REL_L2, (tag, k, e)
-            worst = max(worst, ratio(e, e32g))
+            ratio(e, e32g, k)
+    if 'grad_fused' in res:
         # the fused step: the same kernels, the same numbers (flat, in the model's parameter order)
         assert rel_l2(res['grad_fused'], res['grad_auto']) < 1e-5, (tag, rel_l2(res['grad_fused'], res['grad_auto']))
     if predict:
         ep, ep32 = np.abs(res['path_h'] - o64['path_h']).max(), np.abs(o32['path_h'] - o64['path_h']).max()
         assert ep <= max(2 * ep32, floor_h), (tag, 'path_h', ep, ep32)
-        worst = max(worst, ratio(ep, ep32))
+        ratio(ep, ep32, 'path_h')
         if 'path_y' in res:
             ey, ey32 = np.abs(res['path_y'] - o64['path_y']).max(), np.abs(o32['path_y'] - o64['path_y']).max()
             assert ey <= max(2 * ey32, floor_h), (tag, 'path_y', ey, ey32)
-            worst = max(worst, ratio(ey, ey32))
+            ratio(ey, ey32, 'path_y')
     ratios[family] = max(ratios.get(family, 0.0), worst)
-    print('{:40s} worst err(HIP, f64) / err(o32, f64) = {:.2f}'.format(tag, worst))
+    print('{:40s} worst err(HIP, f64) / err(o32, f64) = {:.2f}  ({}: {:.2e} / {:.2e})'.format(tag, worst, *worst_of))

@@ -118,12 +118,17 @@ ENVS = {
 }
 
 
-def model_cfg(c, dropout=0.0):
+def model_cfg(c, dropout=0.0, which_loss=None, weight=None):
     d, H, DO, nh, W, act, masked, curt, res, rnn = c
     nn = None if nh == 0 else tuple((W, 'relu' if act == RELU else 'tanh') for _ in range(nh))
     opts = {'masked': bool(masked), 'input_current_t': bool(curt), 'residual_enc_dec': bool(res)}
-    return dict(input_size=d, hidden_size=H, output_size=DO, ode_nn=nn, readout_nn=nn, enc_nn=nn,
-                use_rnn=bool(rnn), bias=True, dropout_rate=dropout, options=opts)
+    cfg = dict(input_size=d, hidden_size=H, output_size=DO, ode_nn=nn, readout_nn=nn, enc_nn=nn,
+               use_rnn=bool(rnn), bias=True, dropout_rate=dropout, options=opts)
+    if which_loss is not None:
+        opts['which_loss'] = which_loss
+    if weight is not None:
+        cfg['weight'] = weight
+    return cfg
 
 
 def make_batch(kind, c):
@@ -150,16 +155,43 @@ def make_batch(kind, c):
     return b, meta['dt'], meta['maturity']
 
 
+# steps of the tail of an ``until_T`` job past the last observation: off the grid of delta_t
+TAIL_STEPS = 2.6
+
+
+def job_batch(job, c):
+    """(batch, delta_t, T) of a job: ``make_batch`` of its kind, then the job's optional keys --
+    ``irregular`` (``hip_util.irregular_batch`` with ``dt_factor``), ``dt_factor`` alone (delta_t scaled),
+    ``until_T`` (T a few off-grid steps past the last observation).  Parent and child build the same."""
+    b, dt, T = make_batch(job['batch'], c)
+    if job.get('irregular'):
+        b, dt = hip_util.irregular_batch(b, dt, job['dt_factor'])
+    elif job.get('dt_factor'):
+        dt = job['dt_factor'] * dt
+    if job.get('until_T'):
+        T = float(b['times'][-1]) + TAIL_STEPS * dt
+    return b, dt, T
+
+
+def job_cfg(job, c, dropout=0.0):
+    return model_cfg(c, dropout, job.get('which_loss'), job.get('weight'))
+
+
+def c_hT(B, H):
+    """Upstream gradient of hT of an ``until_T`` job's autograd objective, loss + (c hT).sum()."""
+    return 0.05 * torch.cos(torch.arange(B * H, dtype=torch.float32)).view(B, H)
+
+
 # ---- child side --------------------------------------------------------------------------------------
 def _child(jobs, out_dir):
     """Run every job of this environment; write its numbers (.npz) and kernel names (.json)."""
     meta = {}
     for job in jobs:
         c = tuple(job['cfg'])
-        b, dt, T = make_batch(job['batch'], c)
+        b, dt, T = job_batch(job, c)
         torch.manual_seed(0)
         from njode_amd import models
-        m = hip_model(model_cfg(c, job['dropout']), models.NJODE(**model_cfg(c)).state_dict()).train()
+        m = hip_model(job_cfg(job, c, job['dropout']), models.NJODE(**model_cfg(c)).state_dict()).train()
         ws = []
         acq = m._acquire_ws
         m._acquire_ws = lambda n, dev: (ws.append(int(n)), acq(n, dev))[1]
@@ -169,21 +201,35 @@ def _child(jobs, out_dir):
         m._step_counter = 7
         (_, loss), names = kernel_names(lambda: m.loss_and_grad(*args, M=M))
         res = {'loss_fused': float(loss), 'grad_fused': m.flat_grad().cpu().numpy().astype(np.float64)}
+        # optional keys: an upstream gradient that is not 1; a tail after the last observation, which the
+        # fused step does not take (it moves hT, not the loss) -- with a gradient through hT
+        scale, until = job.get('grad_scale', 1.0), bool(job.get('until_T'))
+        kw = dict(M=M, until_T=True) if until else dict(M=M)
+        if until:
+            del res['grad_fused']
         # the reference's call sequence
         m._step_counter = 7
         m.zero_grad()
 
         def autograd_step():
-            hT, loss2 = m(*args, M=M)
-            loss2.backward()
+            hT, loss2 = m(*args, **kw)
+            if until:
+                (scale * loss2 + (c_hT(*hT.shape).cuda() * hT).sum()).backward()
+            elif scale != 1.0:
+                (scale * loss2).backward()
+            else:
+                loss2.backward()
             return hT, loss2
         (hT, loss2), names2 = kernel_names(autograd_step)
         res['loss_auto'] = float(loss2)
         res['grad_auto'] = np.concatenate([p.grad.detach().cpu().numpy().ravel() for p in m.parameters()])
+        if scale != 1.0:   # (compared with the fused step's, whose upstream gradient is 1)
+            res['grad_auto'] = res['grad_auto'].astype(np.float64) / scale
         res['hT'] = hT.detach().cpu().numpy().astype(np.float64)
         for k, p in m.named_parameters():
             res['g.' + k] = p.grad.detach().cpu().numpy().astype(np.float64)
-        info = {'names': names, 'names_auto': names2, 'ws': ws[0], 'n_obs': int(b['time_ptr'][-1])}
+        info = {'names': names, 'names_auto': names2, 'ws': ws[0], 'n_obs': int(b['time_ptr'][-1]),
+                'B': len(b['start_X'])}
         if job.get('prefetch'):
             # the deferred plan of a call the single launch does not build; must give the same bits
             m._step_counter = 7
@@ -199,6 +245,15 @@ def _child(jobs, out_dir):
                 (out, names4) = kernel_names(lambda: m(*args, M=M, return_path=True))
             res['path_h'] = out[3].cpu().numpy().astype(np.float64)
             info['names_predict'] = names4
+        if job.get('predict_loss'):
+            # the lockstep prediction call with its own loss code, up to T
+            m.eval()
+            with torch.no_grad():
+                (out, names5) = kernel_names(lambda: m(*args, M=M, return_path=True, get_loss=True, until_T=True))
+            res.update({'p.hT': out[0].cpu().numpy().astype(np.float64), 'p.loss': float(out[1]),
+                        'p.path_h': out[3].cpu().numpy().astype(np.float64),
+                        'p.path_y': out[4].cpu().numpy().astype(np.float64)})
+            info['names_predict_loss'] = names5
         np.savez(os.path.join(out_dir, job['id'] + '.npz'), **res)
         meta[job['id']] = info
     with open(os.path.join(out_dir, 'meta.json'), 'w') as f:
@@ -277,20 +332,25 @@ def test_route_table_covers_every_compiled_configuration():
         assert routes(c), ('no route for', c)
 
 
+def check_sizes(kind, n_obs, B):
+    """The row and path counts a batch kind stands for (the tile bounds of its route)."""
+    if kind == 'tiles384':
+        assert (n_obs + 15) // 16 <= 384, n_obs
+    if kind == 'tiles768':
+        assert 384 < (n_obs + 15) // 16 <= 768, n_obs
+    if kind == 'tile1':
+        assert n_obs <= 16, n_obs
+    if kind == 'large':
+        assert (n_obs + 15) // 16 > 2048 and n_obs + B > 16384, (n_obs, B)
+
+
 def _check_row(jid, c, kind, must, must_not, predict, res, info):
     check_names(jid, info['names'], must, must_not)
     check_names(jid + ' (autograd)', info['names_auto'], [m for m in must if 'dw_stored' not in m and 'dw_pairs' not in m], must_not)
     if predict:
         # a prediction call: the lockstep plan, never the segment plan's kernels
         check_names(jid + ' (return_path)', info['names_predict'], [], ITEMS + MIXED)
-    if kind == 'tiles384':
-        assert (info['n_obs'] + 15) // 16 <= 384, info['n_obs']
-    if kind == 'tiles768':
-        assert 384 < (info['n_obs'] + 15) // 16 <= 768, info['n_obs']
-    if kind == 'tile1':
-        assert info['n_obs'] <= 16, info['n_obs']
-    if kind == 'large':
-        assert (info['n_obs'] + 15) // 16 > 2048 and info['n_obs'] + len(res['hT']) > 16384
+    check_sizes(kind, info['n_obs'], len(res['hT']))
     check_vs_oracle(jid, jid.split('_', 1)[1], c, kind, res, predict=predict)
 
 

@@ -558,3 +558,67 @@ def test_hosting_the_plan_does_not_cost_the_ode_forward_a_wave():
     for key, h in hosted.items():
         p = plain[key]
         assert h['occupancy'] == p['occupancy'] and h['vgpr_spill'] == 0, (key, h, p)
+
+
+# ---- the options matrix's inputs (tests/test_hip_options_matrix.py) -------------------------------------
+def _options_shapes():
+    import test_hip_route_matrix as R
+    return [(R.DEMO, 'small'), (R.PHYSIO, 'physio'), (R.DEMO, 'tile1')]
+
+
+def test_irregular_batch_keeps_the_collate_invariants():
+    import hip_util
+    import test_hip_route_matrix as R
+    for c, kind in _options_shapes():
+        b0, dt, T = R.make_batch(kind, c)
+        b, delta_t = hip_util.irregular_batch(b0, dt, 0.37)
+        b_again, _ = hip_util.irregular_batch(R.make_batch(kind, c)[0], dt, 0.37)
+        times, ptr, idx = b['times'], b['time_ptr'], b['obs_idx'].numpy()
+        B = len(b['start_X'])
+        assert delta_t == 0.37 * dt
+        for k in ('times', 'time_ptr'):
+            assert np.array_equal(b[k], b_again[k])
+        assert all(torch.equal(b[k], b_again[k]) for k in ('X', 'obs_idx', 'n_obs_ot'))   # a pure function
+        assert len(times) + 1 == len(ptr) and ptr[0] == 0 and ptr[-1] == len(idx) == len(b['X'])
+        assert np.all(np.diff(times) > 0) and times[0] == 0.0 and times[-1] == b0['times'][-1]
+        assert np.all(np.diff(ptr) >= 0)
+        empty = np.nonzero(np.diff(ptr) == 0)[0]
+        assert len(empty) and any(0 < e < len(times) - 1 for e in empty)   # an empty slice strictly inside
+        assert ptr[-1] > ptr[-2]                                           # the last slice has rows
+        for i in range(len(times)):
+            rows = idx[ptr[i]:ptr[i + 1]]
+            assert np.all(np.diff(rows) > 0)   # sorted by path, at most one row per path and slice
+        assert idx[0] == 0 and ptr[1] >= 1     # the t = 0 jump of path 0
+        assert np.array_equal(b['n_obs_ot'].numpy(), np.bincount(idx, minlength=B))
+        gone = np.nonzero(b['n_obs_ot'].numpy() == 0)[0]
+        assert len(gone) >= 1 and 0 not in gone and idx[-1] not in gone
+        if 'M' in b:
+            assert b['M'].shape == b['X'].shape and bool((b['M'].sum(1) > 0).all())
+        # the schedule the rows rely on
+        s = Schedule(times, delta_t, T, False)
+        assert len(set(s.step_dt.tolist())) >= 2 and not s.has_tail() and s.k_jump[0] == 0 and s.n_steps < 512
+
+
+@pytest.mark.parametrize('shape', [0, 1])
+def test_options_rows_see_a_swapped_weight_and_the_other_loss_form(shape):
+    """The oracle's loss of the two row kinds is more than 1 % away from the loss with weight and
+    1 - weight swapped and from the loss of the other form: the rows cannot go blind to either."""
+    import hip_util
+    import test_hip_options_matrix as O
+    import test_hip_route_matrix as R
+    c, kind = _options_shapes()[shape]
+    torch.manual_seed(0)
+    sd = {k: v.detach().clone() for k, v in models.NJODE(**R.model_cfg(c)).state_dict().items()}
+    other = {'easy': 'standard', 'standard': 'easy'}
+    for rk, opts in O.ROW_KINDS.items():
+        job = dict({'id': rk, 'cfg': list(c), 'batch': kind}, **opts)
+        b, dt, T = R.job_batch(job, c)
+
+        def loss(which, weight):
+            with torch.no_grad():
+                out, _ = hip_util.oracle_forward(R.model_cfg(c, 0.0, which, weight), sd, b, dt, T)
+            return float(out[1])
+        w, which = opts['weight'], opts['which_loss']
+        right = loss(which, w)
+        for wrong in (loss(which, 1 - w), loss(other[which], w)):
+            assert abs(wrong - right) > 0.01 * abs(right), (rk, kind, right, wrong)
