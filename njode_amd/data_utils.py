@@ -137,7 +137,9 @@ def collate_arrays(stock_paths, observed_dates, nb_obs, dt, functions=()):
     times = clock[used]
     time_ptr = np.concatenate([[0], np.cumsum(per_time[used])]).astype(np.int64)
     X = lift(stock_paths[b_idx, :, t_idx + 1], axis=1)
-    X = X.reshape(len(b_idx), -1)
+    # (explicit width: a batch without any observation has an X of [0, width], which
+    # reshape(0, -1) cannot infer)
+    X = X.reshape(len(b_idx), stock_paths.shape[1] * (1 + len(functions)))
     start_X = lift(stock_paths[:, :, 0], axis=1)
     return {'times': times, 'time_ptr': time_ptr,
             'obs_idx': torch.tensor(b_idx, dtype=torch.long),

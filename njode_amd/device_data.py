@@ -57,6 +57,21 @@ def times_from_counts(counts, dt):
     return clock[used], time_ptr
 
 
+def _host_rows(idx, n_paths):
+    """Host row indices as a contiguous int32 array; ``ValueError`` for a row outside
+    ``[0, n_paths)`` or of a non-integer type -- the collate kernels index the dataset with
+    these values unchecked."""
+    rows = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
+    if rows.size and not (np.issubdtype(rows.dtype, np.integer) and rows.dtype != np.uint64):
+        # (floats would be truncated silently; a Python int beyond int64 arrives as object / uint64)
+        raise ValueError('dataset rows must be integers that fit int64, not {}'.format(rows.dtype))
+    rows = rows.astype(np.int64).reshape(-1)
+    if rows.size and (rows.min() < 0 or rows.max() >= n_paths):
+        bad = rows[(rows < 0) | (rows >= n_paths)][0]
+        raise ValueError('dataset row {} outside [0, {})'.format(int(bad), n_paths))
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
 class DeviceDataset:
     """Synthetic dataset resident on one GPU."""
 
@@ -146,11 +161,20 @@ class DeviceDataset:
 
         The per-time counts must reach the host before ``X`` can be sized, so the call waits for
         its own first kernel (``prepare_batches`` + ``fill_batch`` is the form without a wait per
-        batch: one host round trip per epoch)."""
+        batch: one host round trip per epoch).
+
+        Rows given on the host (a list, a numpy array, a CPU tensor) are checked: ``ValueError``
+        for a row outside ``[0, n_paths)`` or a non-integer one, before anything is launched.  A
+        device tensor is used as it is, unchecked -- a check would cost a host wait per batch --
+        so its rows are the caller's responsibility: the kernels read the dataset at whatever
+        row they are given."""
         L = _lib.lib()
         dev = self.device
         if idx is not None:
-            idx = torch.as_tensor(idx, device=dev).to(torch.int32).contiguous()
+            if torch.is_tensor(idx) and idx.device.type != 'cpu':
+                idx = idx.to(dev).to(torch.int32).contiguous().reshape(-1)
+            else:
+                idx = torch.from_numpy(_host_rows(idx, self.n_paths)).to(dev)
             B = idx.numel()
         else:
             B = self.n_paths
@@ -188,13 +212,15 @@ class DeviceDataset:
         copy and the host waits ONCE -- a training loop at the reference's batch sizes
         (B = 100 / 200) is host-bound, and the per-batch wait for its own count kernel was the
         largest item of its step.  ``idx_list``: dataset rows of each batch (array-likes on the
-        host, in batch order).  Returns one descriptor per batch for ``fill_batch``."""
+        host, in batch order); ``ValueError`` for a row outside ``[0, n_paths)``, before anything is
+        uploaded or launched.  Returns one descriptor per batch for ``fill_batch``."""
         L = _lib.lib()
         dev = self.device
         sizes = [len(ix) for ix in idx_list]
         if not sizes or min(sizes) <= 0:
             raise ValueError('empty batch')
-        flat = np.concatenate([np.asarray(ix, dtype=np.int32) for ix in idx_list])
+        flat = _host_rows(np.concatenate([np.asarray(ix).reshape(-1) for ix in idx_list]),
+                          self.n_paths)
         idx_dev = torch.as_tensor(flat).to(dev)                       # one upload per epoch
         n = len(sizes)
         counts = torch.empty((n, self.n_steps), dtype=torch.int32, device=dev)

@@ -9,10 +9,15 @@ restates that generator (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: a
 checked word for word, and is itself pinned to the algorithm's published known-answer
 vectors (Random123 ``kat_vectors``) in tests/test_producer_oracle.py.
 
-The SDE recurrences and the collate have no separate restatement here: the host versions in
-``njode_amd/stock_model.py`` / ``njode_amd/data_utils.py`` are already pinned to the
-reference's outputs by tests/golden (G4) and serve as the checker for the device kernels.
+``philox_dataset`` is the dataset ``DeviceDataset.generate(name, hp, seed)`` must produce: the
+streams above fed through the HOST generators of ``njode_amd/stock_model.py`` (their
+``np.random.normal`` call is handed the oracle's array for the duration of the call), so the
+SDE recurrences are written once, in the generators that tests/golden (G4) pins to the
+reference's outputs; the host collate of ``njode_amd/data_utils.py`` is the checker of the
+device collate in the same way.
 """
+import contextlib
+
 import numpy as np
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -85,3 +90,55 @@ def path_normals(n_paths, n_steps, dim, seed):
     z1 = (rad * np.cos(2.0 * np.pi * u2)).reshape(n_paths, n_steps, dim)
     z2 = (rad * np.sin(2.0 * np.pi * u2)).reshape(n_paths, n_steps, dim)
     return z1, z2
+
+
+@contextlib.contextmanager
+def _normal_draws(z):
+    """For the duration of the block ``np.random.normal(0, 1, z.shape)`` returns ``z`` -- how
+    the host generators, which draw from numpy's global stream, are handed other draws without
+    touching product code.  One call only, of exactly that shape."""
+    real, calls = np.random.normal, []
+
+    def fake(loc=0.0, scale=1.0, size=None):
+        assert (loc, scale) == (0, 1) and tuple(np.atleast_1d(size)) == z.shape and not calls, \
+            (loc, scale, size, z.shape, len(calls))
+        calls.append(1)
+        return z.copy()
+
+    np.random.normal = fake
+    try:
+        yield
+    finally:
+        np.random.normal = real
+    assert calls, 'the generator drew nothing'
+
+
+def host_dataset(name, hp, normals, uniforms):
+    """The host generator of model ``name`` (``njode_amd/stock_model.py``) run on the given
+    draws: ``normals`` f64 [N, S, d] (Heston: [N, S, 2, d]), ``uniforms`` f64 [N, S+1].
+    Returns (paths [N, d, S+1], observed int [N, S+1], nb_obs int [N]) as ``create_dataset``
+    does."""
+    from njode_amd import stock_model
+    hp = dict(hp)
+    model = stock_model.STOCK_MODELS[name](**hp)
+    with _normal_draws(np.asarray(normals, dtype=np.float64)):
+        paths, _ = model.generate_paths()
+    observed = (np.asarray(uniforms) < hp['obs_perc']) * 1
+    return paths, observed, np.sum(observed[:, 1:], axis=1)
+
+
+def dataset_draws(name, hp, seed):
+    """(normals, uniforms) that ``njode_generate_paths`` / ``njode_sample_observations`` consume
+    for ``seed``, in the host generators' layout."""
+    n, s, d = int(hp['nb_paths']), int(hp['nb_steps']), int(np.size(hp.get('S0', 1)))
+    if name == 'Heston':
+        normals = np.stack(path_normals(n, s, d, seed), axis=2)      # [N, S, 2, d]
+    else:
+        normals = step_normals(n, s, d, seed)
+    return normals, observation_uniforms(n, s, seed)
+
+
+def philox_dataset(name, hp, seed):
+    """The dataset ``DeviceDataset.generate(name, hp, seed)`` (no supplied draws) stands for:
+    (paths f64 [N, d, S+1], observed int [N, S+1], nb_obs int [N])."""
+    return host_dataset(name, hp, *dataset_draws(name, hp, seed))
