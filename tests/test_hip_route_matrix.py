@@ -2,8 +2,8 @@
 
 The library picks one of about six kernel families per call from the model shape (the
 shape-specialised table ``njode_amd.build.CONFIGS``), the batch size, the row count, the Euler-step
-count K and the record budget (``njode_api.hip``: ``chain_paths``, ``seg_chain_items``,
-``make_layout``, ``prepare``).  This module derives the routes of every configuration from the
+count K and the record budget (``njode_route.h``: ``size_call`` decides what the workspace is sized
+for, ``route_call`` what ``njode_api.hip`` launches).  This module derives the routes of every configuration from the
 kernels' capability predicates (restated below), drives each one on purpose -- through batch sizes,
 schedule lengths and the A/B environment switches -- and checks that the route ran by the kernel
 names of ``njode_profile_read``.  Every route's loss, hT and gradients are compared with the oracle
@@ -454,9 +454,9 @@ CHAIN_ACT_FLOATS = 128                           # njode_kernels.h
 
 
 def _budgets():
-    """NJODE_REC_BUDGET_GB values: (middle, tiny).  chain_paths() / seg_chain_items() keep the records
-    while B K (CHAIN_ACT_FLOATS 4 + 16) bytes fit, make_layout() the deltas while B K (2 CHAIN_ACT_FLOATS 4
-    + 16) do."""
+    """NJODE_REC_BUDGET_GB values: (middle, tiny).  size_call() (njode_route.h) keeps the records (Sizing::chain,
+    seg_items) while B K (CHAIN_ACT_FLOATS 4 + 16) bytes fit, the deltas (Sizing::delta) while B K (2
+    CHAIN_ACT_FLOATS 4 + 16) do."""
     from njode_amd.schedule import Schedule
     bk = []
     for kind, c in (('small', DEMO), ('physio', PHYSIO)):
@@ -483,7 +483,7 @@ def test_record_budget_routes(tmp_path):
                                    {'NJODE_REC_BUDGET_GB': repr(mid), 'NJODE_CHAIN_DELTA': '0'}, jobs)
     got['tiny'] = run_child(tmp_path, 'budget_tiny', {'NJODE_REC_BUDGET_GB': repr(tiny)}, jobs + gen)
     # (the paths per tile the budget picks for the masked batch: 37 paths of 60 steps cannot fit any
-    # tile's records at this budget, so q4_paths_per_tile goes up to 16)
+    # tile's records at this budget, so Sizing::q4_pt goes up to 16)
     got['tiny_tiles'] = run_child(tmp_path, 'budget_tiny_tiles',
                                   {'NJODE_REC_BUDGET_GB': repr(tiny), 'NJODE_SEG_CHAIN_MAX': '0',
                                    'NJODE_CHAIN_MAX': '0', 'NJODE_LOCK4_PT': '16', 'NJODE_GEN_PT': '16'},
