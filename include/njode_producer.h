@@ -9,6 +9,8 @@
  *   njode_sample_observations  data_utils.py:73-81 (observation mask of create_dataset)
  *   njode_collate_count/_fill  data_utils.py:278-316 (custom_collate_fn) and
  *                              :352-416 (CustomCollateFnGen, func_appl_X = power-k)
+ *   njode_cond_exp_f64         stock_model.py:50-158 (compute_cond_exp, get_optimal_loss),
+ *                              :178, :353, :393 (next_cond_exp), :471-481 (compute_loss)
  *
  * Conventions are those of njode_hip.h (device pointers, caller-owned buffers, caller's
  * stream, int return code + njode_last_error()).
@@ -82,6 +84,54 @@ int njode_collate_fill(const double* paths_tm, const uint8_t* observed_tm, int32
                        int32_t dim, int32_t n_steps, const int32_t* batch_idx, int32_t B,
                        const int32_t* count_per_time, const int32_t* powers, int32_t n_powers,
                        float* start_X, float* X, int32_t* obs_idx, njodeStream_t stream);
+
+/* ---- analytic conditional expectation and the metrics taken against it -----------------
+ * Reference: stock_model.py:50-158 (compute_cond_exp, get_optimal_loss), :178 / :353 / :393
+ * (next_cond_exp of Heston / BlackScholes / OrnsteinUhlenbeck), :471-481 (compute_loss).
+ *
+ * The float64 clock of the walk, HOST (or pinned) arrays.  NjodeSchedule's fp32 roundings are
+ * not enough here: the factor of a step is exp(rate * periodic_coeff(step_t) * step_dt) in
+ * float64.  Python: schedule.cond_exp_clock. */
+typedef struct NjodeCondExpSchedule {
+  int32_t n_steps;         /* K: Euler steps up to T                                   */
+  int32_t n_times;         /* number of observation times                              */
+  const double* step_dt;   /* [K] length of step k                                     */
+  const double* step_t;    /* [K] clock before step k                                  */
+  const int32_t* k_jump;   /* [n_times] Euler steps completed when jump i happens      */
+  const int32_t* time_ptr; /* [n_times + 1] rows of X per observation time (CSR)       */
+} NjodeCondExpSchedule;
+
+/* workspace of one call, in bytes */
+int njode_cond_exp_bytes(int32_t B, int32_t n_obs, int32_t n_times, int32_t n_steps, int32_t dim,
+                         size_t* out);
+
+/* The true conditional expectation of `sde` along the batch's schedule, walked in float64 from
+ * start_X (fp32 inputs are widened exactly): per Euler step y = y * a_k + c_k with
+ * a_k = exp(rate * periodic_coeff(step_t[k]) * step_dt[k]) (rate = drift; OrnsteinUhlenbeck:
+ * -speed and c_k = mean * (1 - a_k), else c_k = 0), at jump i y[obs_idx[r]] = X[r] for the rows
+ * of slice i.  Rows of the path: [start | one per Euler step | one per jump] in the order of
+ * the clock (the model's path_y of a RETURN_PATH call with the until-T tail).
+ *
+ * Of `sde` only model, dim, has_sine, sine_coeff, drift, mean and speed are read (n_paths and
+ * n_steps are ignored); of `batch` batch_size, n_obs, start_X [B][dim], X [n_obs][dim],
+ * obs_idx and n_obs_ot (device pointers; at most one row per path and time slice).
+ *
+ * Outputs (device, each may be NULL, not all three):
+ *   path_y   f64 [1 + K + n_times][B][dim]
+ *   opt_loss f64 [1]  loss of the true conditional expectation: the sum over the rows of
+ *                     (2 w sqrt(eps) + 2 (1 - w) sqrt(sum_d (y_before_jump - X)^2 + eps))^2
+ *                     / n_obs_ot[path], divided by B; eps = 1e-10, w = weight
+ *   sq_diff  f64 [1]  sum over all rows, paths and dims of (pred - path_y)^2 against
+ *                     pred fp32 [1 + K + n_times][B][dim]; the path is not stored for it
+ * Sums are reduced in a fixed order: the same call gives the same bits.
+ *
+ * NJODE_E_BADARG: null or negative arguments, no output, sq_diff without pred, opt_loss
+ * without n_obs_ot, a non-NULL batch->M, an unknown model, a time_ptr / k_jump that is not a
+ * schedule of this batch.  NJODE_E_WORKSPACE: ws_bytes too small. */
+int njode_cond_exp_f64(const NjodeSde* sde, const NjodeBatch* batch,
+                       const NjodeCondExpSchedule* sched, double weight, const float* pred,
+                       double* path_y, double* opt_loss, double* sq_diff, void* ws,
+                       size_t ws_bytes, njodeStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            # include/njode_producer.h
            'njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
            'njode_collate_count', 'njode_collate_fill',
+           'njode_cond_exp_bytes', 'njode_cond_exp_f64',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
 SDE_MODELS = {'BlackScholes': 0, 'OrnsteinUhlenbeck': 1, 'Heston': 2}
@@ -74,6 +75,12 @@ class NjodeSde(C.Structure):
                 ('drift', C.c_double), ('volatility', C.c_double), ('mean', C.c_double),
                 ('speed', C.c_double), ('correlation', C.c_double), ('S0', C.c_double),
                 ('maturity', C.c_double), ('sine_coeff', C.c_double)]
+
+
+class NjodeCondExpSchedule(C.Structure):
+    _fields_ = [('n_steps', C.c_int32), ('n_times', C.c_int32),
+                ('step_dt', C.c_void_p), ('step_t', C.c_void_p),
+                ('k_jump', C.c_void_p), ('time_ptr', C.c_void_p)]
 
 
 class NjodeError(RuntimeError):
@@ -145,8 +152,13 @@ def lib():
     L.njode_collate_count.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
     L.njode_collate_fill.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp,
                                      C.POINTER(C.c_int32), i32, vp, vp, vp, vp]
+    L.njode_cond_exp_bytes.argtypes = [i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.njode_cond_exp_f64.argtypes = [C.POINTER(NjodeSde), C.POINTER(NjodeBatch),
+                                     C.POINTER(NjodeCondExpSchedule), f64, vp, vp, vp, vp, vp, sz,
+                                     vp]
     for name in ('njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
                  'njode_collate_count', 'njode_collate_fill',
+                 'njode_cond_exp_bytes', 'njode_cond_exp_f64',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
         getattr(L, name).restype = C.c_int

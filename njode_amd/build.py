@@ -155,6 +155,8 @@ def build(force=False, jobs=None, verbose=True):
                  '_generated_cfgs.inc')] + [hdr, hdr_self]
     prod_deps = [os.path.join(CSRC, n) for n in ('njode_producer.hip', 'njode_error.h')] + [
         hdr, hdr_prod]
+    ce_deps = [os.path.join(CSRC, n) for n in ('njode_condexp.hip', 'njode_error.h')] + [
+        hdr, hdr_prod]
     tasks = []   # (object, command, digest)
     for i, (d, h, do, nh, w, act, masked, curt, res, rnn) in enumerate(cfgs):
         for part in range(6):
@@ -176,6 +178,10 @@ def build(force=False, jobs=None, verbose=True):
     prod_obj = os.path.join(OBJ, 'producer.o')
     cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_producer.hip'), '-o', prod_obj]
     tasks.append((prod_obj, cmd, _digest(prod_deps, ' '.join(cmd))))
+    # ... and so does the analytic conditional expectation (the host walk's y * a + c, unfused)
+    ce_obj = os.path.join(OBJ, 'condexp.o')
+    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_condexp.hip'), '-o', ce_obj]
+    tasks.append((ce_obj, cmd, _digest(ce_deps, ' '.join(cmd))))
     if os.environ.get('NJODE_RESTAMP'):   # maintainer aid: adopt the objects on disk as current
         for t in tasks:
             if os.path.exists(t[0]):
@@ -190,7 +196,7 @@ def build(force=False, jobs=None, verbose=True):
     todo = [t for t in tasks if stale(t)]
     parts_only = os.environ.get('NJODE_PARTS_ONLY', '').strip()   # maintainer aid, e.g. "0": a change
     if parts_only:                                                 # that only touches those parts
-        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'gen.o')
+        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'gen.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
                 with open(t[0] + '.stamp', 'w') as f:

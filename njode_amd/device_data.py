@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .schedule import PinnedRing, cond_exp_clock
 
 _HP_KEYS = ('drift', 'volatility', 'mean', 'speed', 'correlation', 'S0', 'maturity')
 
@@ -44,6 +45,143 @@ def parse_powers(func_names):
     if len(out) > 4:
         raise ValueError('at most 4 func_appl_X entries')
     return out
+
+
+def sde_struct(stock_model_name, hp, dim):
+    """``NjodeSde`` of a model name and its hyper-parameter dict (``create_dataset``'s
+    ``hyperparam_dict`` / a dataset's metadata); vector-valued entries contribute their first
+    component.  ``sine_<Model>`` names the same model (its ``sine_coeff`` is in the dict)."""
+    name = stock_model_name[5:] if stock_model_name.startswith('sine_') else stock_model_name
+    if name not in _lib.SDE_MODELS:
+        raise ValueError('no analytic model named {!r}'.format(stock_model_name))
+    sde = _lib.NjodeSde()
+    sde.model = _lib.SDE_MODELS[name]
+    sde.n_paths, sde.dim, sde.n_steps = int(hp.get('nb_paths', 0)), int(dim), int(hp.get('nb_steps', 0))
+    sc = hp.get('sine_coeff')
+    sde.has_sine, sde.sine_coeff = (0, 0.0) if sc is None else (1, float(sc))
+    for k in _HP_KEYS:
+        v = hp.get(k)
+        setattr(sde, k, float(np.ravel(v)[0]) if v is not None else 0.0)
+    return sde
+
+
+def _sde_of(sde, dim):
+    """``NjodeSde`` of a ``stock_model`` object or a metadata dict, for inputs ``dim`` wide."""
+    if isinstance(sde, dict):
+        if 'model_name' not in sde:
+            raise ValueError("a metadata dict needs 'model_name'")
+        name, hp = sde['model_name'], sde
+        own = int(np.size(sde.get('S0', 1)))      # (StockModel.dimensions)
+    else:
+        name = type(sde).__name__
+        hp = {k: getattr(sde, k, None) for k in _HP_KEYS + ('sine_coeff',)}
+        own = int(sde.dimensions)
+    if own != dim:
+        # (func_appl_X lifts append columns that have no analytic truth: the host route reports nan)
+        raise ValueError('inputs are {} wide but the model has {} dimensions (lifted inputs have '
+                         'no analytic conditional expectation)'.format(dim, own))
+    return sde_struct(name, hp, dim)
+
+
+_ring = None
+
+
+def cond_exp(sde, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot=None, weight=0.5,
+             pred=None, want_path=False, want_loss=False, M=None, start_time=None):
+    """``StockModel.compute_cond_exp`` (``start_time=None``) on the GPU: the true conditional
+    expectation of ``sde`` (a ``stock_model`` object or a dataset's metadata dict) along the
+    batch's schedule, in float64, and the metrics taken against it.  Returns
+    ``(path_t, path_y, opt_loss, sq_diff)``:
+
+    * ``path_t``  float64 numpy ``[n_t]`` -- the host walk's ``path_t``;
+    * ``path_y``  float64 device ``[n_t, B, d]`` with ``want_path``, else None;
+    * ``opt_loss`` 0-dim float64 device tensor with ``want_loss`` (needs ``n_obs_ot``): what
+      ``get_optimal_loss(..., weight=weight)`` returns, else None;
+    * ``sq_diff`` 0-dim float64 device tensor with ``pred`` (fp32 ``[n_t, B, d]``, the model's
+      ``path_y`` of a ``return_path=True, until_T=True`` call): the sum of ``(pred - path_y)**2``
+      over all entries, taken without storing the path; else None.
+
+    A path has at most one row per time slice (what the collate produces); this is the caller's
+    duty and is not checked -- a check would cost a host wait: with a duplicate (slice, path)
+    pair it is undefined which row the path takes, and the results are no longer reproducible.
+
+    Tensors stay on the device and nothing here waits for it.  ``ValueError``, before anything
+    is launched: ``times`` not strictly increasing within ``(0, T + 1e-10]``, lifted inputs, a
+    mask ``M``, a ``start_time``, no output asked for, ``want_loss`` without ``n_obs_ot``."""
+    global _ring
+    if M is not None:
+        raise ValueError('masked batches have no analytic conditional expectation')
+    if start_time:
+        raise ValueError('start_time is not supported: the walk starts at 0')
+    if not (want_path or want_loss or pred is not None):
+        raise ValueError('nothing asked for: want_path, want_loss or pred')
+    if want_loss and n_obs_ot is None:
+        raise ValueError('want_loss needs n_obs_ot')
+    if start_X.dim() != 2 or X.dim() != 2 or X.shape[1] != start_X.shape[1]:
+        raise ValueError('start_X must be [B, d] and X [n_obs, d]')
+    B, dim = int(start_X.shape[0]), int(start_X.shape[1])
+    if B == 0:
+        raise ValueError('empty batch')
+    cs = _sde_of(sde, dim)
+    clock = cond_exp_clock(times, delta_t, T)
+    tp = np.ascontiguousarray(time_ptr, dtype=np.int64).reshape(-1)
+    n_obs = int(X.shape[0])
+    if len(tp) != clock.n_times + 1 or tp[0] != 0 or tp[-1] != n_obs or np.any(np.diff(tp) < 0):
+        raise ValueError('time_ptr must have len(times) + 1 non-decreasing entries from 0 to len(X)')
+    if obs_idx.numel() != n_obs:
+        raise ValueError('obs_idx must have one entry per row of X')
+    K, nt = clock.n_steps, clock.n_times
+    n_t = 1 + K + nt
+    if pred is not None and tuple(pred.shape) != (n_t, B, dim):
+        raise ValueError('pred must be [{}, {}, {}], not {}'.format(n_t, B, dim, tuple(pred.shape)))
+
+    dev = start_X.device
+    if dev.type != 'cuda':
+        raise RuntimeError('device_data.cond_exp runs on the GPU only (inputs are on {}); the host '
+                           'route is stock_model.compute_cond_exp'.format(dev))
+    L = _lib.lib()
+    f32, f64 = torch.float32, torch.float64
+    start_X = start_X.to(f32).contiguous()
+    X = X.to(device=dev, dtype=f32).contiguous()
+    obs_idx = obs_idx.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+    if n_obs_ot is not None:
+        n_obs_ot = n_obs_ot.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+        if n_obs_ot.numel() != B:
+            raise ValueError('n_obs_ot must have one entry per path')
+    if pred is not None:
+        pred = pred.to(device=dev, dtype=f32).contiguous()
+    # the float64 clock travels through a pinned buffer: [step_dt | step_t | k_jump | time_ptr]
+    if _ring is None:
+        _ring = PinnedRing()
+    slot, pinned = _ring.acquire(16 * K + 4 * (2 * nt + 1))
+    buf = pinned.numpy()
+    d = buf[:4 * K].view(np.float64)
+    d[:K] = clock.step_dt
+    d[K:] = clock.step_t
+    buf[4 * K:4 * K + nt] = clock.k_jump
+    buf[4 * K + nt:4 * K + 2 * nt + 1] = tp
+    base = pinned.data_ptr()
+    sched = _lib.NjodeCondExpSchedule(K, nt, base, base + 8 * K, base + 16 * K, base + 16 * K + 4 * nt)
+    batch = _lib.NjodeBatch(B, n_obs, start_X.data_ptr(), X.data_ptr() if n_obs else None, None,
+                            obs_idx.data_ptr() if n_obs else None,
+                            n_obs_ot.data_ptr() if n_obs_ot is not None else None, float(B), 0, None)
+    need = C.c_size_t(0)
+    _lib.check(L.njode_cond_exp_bytes(B, n_obs, nt, K, dim, C.byref(need)))
+    ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+    path_y = torch.empty((n_t, B, dim), dtype=f64, device=dev) if want_path else None
+    # (one allocation for both scalars: a caller that reads both fetches them in one copy)
+    scal = torch.empty(2, dtype=f64, device=dev)
+    opt_loss = scal[0] if want_loss else None
+    sq_diff = scal[1] if pred is not None else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        try:
+            _lib.check(L.njode_cond_exp_f64(
+                C.byref(cs), C.byref(batch), C.byref(sched), float(weight), _ptr(pred), _ptr(path_y),
+                _ptr(opt_loss), _ptr(sq_diff), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)))
+        finally:
+            _ring.release_after(slot, stream)
+    return clock.path_t.copy(), path_y, opt_loss, sq_diff
 
 
 def times_from_counts(counts, dt):
@@ -102,14 +240,12 @@ class DeviceDataset:
         dim = int(np.size(hp.get('S0', 1)))
         if dim != 1 and np.ptp(np.asarray(hp['S0'], dtype=np.float64)) != 0:
             raise ValueError('S0 must be the same in every dimension')
-        sde = _lib.NjodeSde()
-        sde.model = _lib.SDE_MODELS[stock_model_name]
-        sde.n_paths, sde.dim, sde.n_steps = int(hp['nb_paths']), dim, int(hp['nb_steps'])
-        sc = hp.get('sine_coeff')
-        sde.has_sine, sde.sine_coeff = (0, 0.0) if sc is None else (1, float(sc))
-        for k in _HP_KEYS:
-            v = hp.get(k)
-            setattr(sde, k, float(np.ravel(v)[0]) if v is not None else 0.0)
+        for key in ('nb_paths', 'nb_steps'):
+            if key not in hp:
+                raise KeyError(key)
+        if stock_model_name not in _lib.SDE_MODELS:   # (no 'sine_' aliases here: the name is stored)
+            raise KeyError(stock_model_name)
+        sde = sde_struct(stock_model_name, hp, dim)
         N, S = sde.n_paths, sde.n_steps
         paths = torch.empty((S + 1, dim, N), dtype=torch.float64, device=dev)
         observed = torch.empty((S + 1, N), dtype=torch.uint8, device=dev)

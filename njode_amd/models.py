@@ -1009,6 +1009,32 @@ class NJODE(torch.nn.Module):
             return eval_loss, path_t, true_path_t, path_y, true_path_y
         return eval_loss
 
+    def evaluate_device(self, times, time_ptr, X, obs_idx, delta_t, T, start_X, stockmodel,
+                        return_paths=False):
+        """``evaluate`` with the default ``diff_fun`` without leaving the GPU: the prediction
+        path, then ``mean((path_y - true_path_y) ** 2)`` against the analytic conditional
+        expectation of ``stockmodel`` (a ``stock_model`` object or a dataset's metadata dict)
+        from ``device_data.cond_exp`` -- float64, fused: the true path is only stored with
+        ``return_paths``.  Returns a 0-dim float64 device tensor with
+        ``options['device_outputs']``, else a Python float; with ``return_paths`` the tuple
+        ``(eval_loss, path_t, true_path_t, path_y, true_path_y)`` of ``evaluate`` with device
+        tensors.  Unmasked synthetic data only (``ValueError`` for lifted inputs)."""
+        from . import device_data
+        self.eval()
+        with torch.no_grad():
+            _, _, path_t, _, path_y = self.forward(
+                times, time_ptr, X, obs_idx, delta_t, T, start_X, None, return_path=True,
+                get_loss=False, until_T=True)
+        true_path_t, true_path_y, _, sq_diff = device_data.cond_exp(
+            stockmodel, times, time_ptr, X, obs_idx, delta_t, T, start_X, pred=path_y,
+            want_path=return_paths)
+        eval_loss = sq_diff / path_y.numel()
+        if not self.device_outputs:
+            eval_loss = float(eval_loss)
+        if return_paths:
+            return eval_loss, path_t, true_path_t, path_y, true_path_y
+        return eval_loss
+
     def get_pred(self, times, time_ptr, X, obs_idx, delta_t, T, start_X, M=None):
         """Predicted path (reference ``models.py:564-584``)."""
         self.eval()

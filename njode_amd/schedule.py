@@ -21,32 +21,43 @@ import numpy as np
 import torch
 
 
+def _walk_clock(times, delta_t, T, until_T, strict=False):
+    """The float64 clock of one pass: (step lengths, clock before each step, k_jump, path_t,
+    row_of_jump) as Python lists.  ``strict``: ``ValueError`` for an observation time the clock
+    has already reached (the reference's conditional-expectation walk skips those)."""
+    dts, ts, k_jump, path_t, row_of_jump = [], [], [], [0.0], []
+    now = 0.0
+
+    def walk(now, target):
+        guard = target - 1e-10 * delta_t
+        while now < guard:
+            step = delta_t if now < target - delta_t else target - now
+            dts.append(step)
+            ts.append(now)
+            now = now + step
+            path_t.append(now)
+        return now
+
+    for obs_time in times:
+        if strict and not obs_time > now:
+            raise ValueError('observation times must be strictly increasing and positive '
+                             '({!r} after the clock reached {!r})'.format(float(obs_time), now))
+        now = walk(now, obs_time)
+        k_jump.append(len(dts))
+        row_of_jump.append(len(path_t))
+        path_t.append(obs_time)
+    if until_T:
+        now = walk(now, T)
+    return dts, ts, k_jump, path_t, row_of_jump
+
+
 class Schedule:
     __slots__ = ('step_dt', 'step_t', 'k_jump', 'time_f32', 'path_t', 'n_steps', 'n_times',
                  'row_of_jump')
 
     def __init__(self, times, delta_t, T, until_T):
         times = np.asarray(times, dtype=np.float64)
-        dts, ts, k_jump, path_t, row_of_jump = [], [], [], [0.0], []
-        now = 0.0
-
-        def walk(now, target):
-            guard = target - 1e-10 * delta_t
-            while now < guard:
-                step = delta_t if now < target - delta_t else target - now
-                dts.append(step)
-                ts.append(now)
-                now = now + step
-                path_t.append(now)
-            return now
-
-        for obs_time in times:
-            now = walk(now, obs_time)
-            k_jump.append(len(dts))
-            row_of_jump.append(len(path_t))
-            path_t.append(obs_time)
-        if until_T:
-            now = walk(now, T)
+        dts, ts, k_jump, path_t, row_of_jump = _walk_clock(times, delta_t, T, until_T)
         self.step_dt = np.asarray(dts, dtype=np.float64).astype(np.float32)
         self.step_t = np.asarray(ts, dtype=np.float64).astype(np.float32)
         self.k_jump = np.asarray(k_jump, dtype=np.int32)
@@ -80,6 +91,35 @@ class Schedule:
         f[2 * K + nt:2 * K + 2 * nt] = self.time_f32
         buf[2 * K + 2 * nt:2 * K + 3 * nt + 1] = time_ptr
         return K, nt
+
+
+CondExpClock = collections.namedtuple(
+    'CondExpClock', 'step_dt step_t k_jump path_t row_of_jump n_steps n_times')
+
+
+def cond_exp_clock(times, delta_t, T):
+    """The clock of ``stock_model.StockModel.compute_cond_exp`` (``start_time=None``) in float64:
+    ``step_dt`` / ``step_t`` [K] (length of Euler step k, clock before it), ``k_jump`` [n_times]
+    int32, and ``path_t`` -- the host walk's ``path_t``, entry for entry.  It is ``Schedule``'s
+    clock up to ``T`` before the fp32 rounding: the analytic factors are
+    ``exp(rate * periodic_coeff(step_t) * step_dt)`` in float64.
+
+    ``ValueError`` unless ``times`` is strictly increasing with ``0 < times[i] <= T + 1e-10``
+    (the host walk silently skips a time its clock has reached and stops at one beyond ``T``)."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    delta_t, T = float(delta_t), float(T)
+    if not (delta_t > 0 and np.isfinite(delta_t) and np.isfinite(T)):
+        raise ValueError('delta_t must be positive and T finite')
+    if not np.all(np.isfinite(times)):
+        raise ValueError('observation times must be finite')
+    if times.size and (np.any(np.diff(times) <= 0) or times[0] <= 0):
+        raise ValueError('observation times must be strictly increasing and positive')
+    if times.size and times[-1] > T + 1e-10:
+        raise ValueError('observation time {!r} beyond T = {!r}'.format(float(times[-1]), T))
+    dts, ts, k_jump, path_t, row_of_jump = _walk_clock(times, delta_t, T, True, strict=True)
+    return CondExpClock(np.asarray(dts, dtype=np.float64), np.asarray(ts, dtype=np.float64),
+                        np.asarray(k_jump, dtype=np.int32), np.asarray(path_t, dtype=np.float64),
+                        np.asarray(row_of_jump, dtype=np.int64), len(dts), len(times))
 
 
 class ScheduleCache:

@@ -40,6 +40,7 @@ class StockModel:
         self.nb_steps = nb_steps
         self.maturity = maturity
         self.dimensions = np.size(S0)
+        self.sine_coeff = sine_coeff    # (read by device_data.cond_exp)
         if sine_coeff is None:
             self.periodic_coeff = lambda t: 1
         else:

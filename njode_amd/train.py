@@ -70,7 +70,7 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
           evaluate=False, shuffle_seed=0, log=print, max_steps_per_epoch=None,
           device_collate=False, model_path=None, model_id=1, save_every=1,
           resume_training=False, load_best=False, plan_ahead=True, plan_ahead_min=0,
-          init_state=None, **options):
+          init_state=None, device_eval=False, **options):
     """Train on an in-memory dataset ``(stock_paths, observed_dates, nb_obs)`` with
     ``metadata`` as returned by ``data_utils.create_dataset``.  Returns
     ``(model, metrics)`` with one row of ``METR_COLUMNS`` per epoch.
@@ -81,7 +81,10 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
     batch ahead and, for local batches of 4 096 paths or more, build its execution plan beside
     the current step (same results bit for bit).  ``init_state``: a state_dict to start from
     instead of the seed-0 initialisation; ``dropout_seed`` (an option of the model) selects the
-    dropout stream."""
+    dropout stream.  ``device_eval=True``: ``optimal_eval_loss`` and (``evaluate=True``)
+    ``evaluation_mean_diff`` come from the analytic conditional expectation on the GPU
+    (``device_data.cond_exp``, ``NJODE.evaluate_device``) on the validation batch's device copies
+    instead of the host's numpy walk; an epoch's metrics then reach the host in one read."""
     stock_paths, observed_dates, nb_obs = dataset_arrays
     delta_t, T = metadata['dt'], metadata['maturity']
     input_size = output_size = metadata['dimension']
@@ -111,10 +114,18 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
     val = data_utils.collate_arrays(stock_paths[val_idx], observed_dates[val_idx],
                                     nb_obs[val_idx], delta_t, funcs)
     stockmodel = stock_model.STOCK_MODELS[metadata['model_name']](**metadata)
-    opt_eval_loss = compute_optimal_eval_loss(val, stockmodel, delta_t, T) if mult == 1 \
-        else float('nan')
+    if device_eval and mult != 1:
+        raise ValueError('device_eval: lifted inputs (func_appl_X) have no analytic conditional '
+                         'expectation')
+    opt_eval_loss = compute_optimal_eval_loss(val, stockmodel, delta_t, T) \
+        if mult == 1 and not device_eval else float('nan')
     val_d = _device_batch(val, device)
     val_d['n_obs_ot'] = val['n_obs_ot'].to(device, torch.int32)   # eval uses the dataset's count
+    opt_eval_dev = None
+    if device_eval:   # (stays on the device: read with the first epoch's evaluation loss)
+        opt_eval_dev = device_data.cond_exp(
+            stockmodel, val_d['times'], val_d['time_ptr'], val_d['X'], val_d['obs_idx'], delta_t, T,
+            val_d['start_X'], n_obs_ot=val_d['n_obs_ot'], want_loss=True)[2]
 
     dev_ds = device_data.DeviceDataset.from_arrays(stock_paths, observed_dates, nb_obs, metadata,
                                                    device) if device_collate else None
@@ -251,9 +262,21 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
             _, c_loss = model(val_d['times'], val_d['time_ptr'], val_d['X'], val_d['obs_idx'],
                               delta_t, T, val_d['start_X'], val_d['n_obs_ot'],
                               return_path=False, get_loss=True)
-            loss_val = float(c_loss)
             row_extra = []
-            if evaluate:
+            if device_eval:
+                # one host read per epoch: evaluation loss, loss floor and distance together
+                dev_vals = [c_loss.double().reshape(()), opt_eval_dev]
+                if evaluate:
+                    dev_vals.append(model.evaluate_device(
+                        val_d['times'], val_d['time_ptr'], val_d['X'], val_d['obs_idx'], delta_t,
+                        T, val_d['start_X'], stockmodel))
+                host_vals = torch.stack(dev_vals).cpu().tolist()
+                # (fp32 -> float64 is exact: the same number float(c_loss) gives)
+                loss_val, opt_eval_loss = host_vals[0], host_vals[1]
+                row_extra = host_vals[2:]
+            else:
+                loss_val = float(c_loss)
+            if evaluate and not device_eval:
                 row_extra = [model.evaluate(
                     val_d['times'], val_d['time_ptr'], val_d['X'], val['obs_idx'], delta_t, T,
                     val_d['start_X'], val['n_obs_ot'], stockmodel)]
