@@ -33,6 +33,18 @@
  *   - return 0 on success, an NJODE_E_* code otherwise (message via
  *     njode_last_error()).  No exceptions cross the ABI.
  *   - float data is fp32; indices are int32.
+ *   - sizes and alignment of the caller's buffers.  njode_workspace_bytes, njode_plan_bytes and
+ *     njode_cond_exp_bytes are exact promises: a buffer of precisely that many bytes is enough, no
+ *     call reads or writes a byte before or behind it, and the number is what the caller passes as
+ *     workspace_bytes / plan_bytes / ws_bytes.  Input and output arrays have exactly the shapes
+ *     stated at each entry point and are held to them in the same way (tile kernels do not touch
+ *     padded rows behind batch_size or n_obs).  `workspace` and `plan` must be aligned to 256
+ *     bytes: the library lays its sub-buffers out at multiples of 256 bytes from the base
+ *     (Layout::take, njode_api.hip / njode_gen.hip) and reads them with 8-byte words and 16-byte
+ *     vectors.  Every other array (parameters, batch, outputs) has only been tested at the alignment
+ *     of a device allocation's pointer: tests/test_hip_buffer_bounds.py calls every entry point at
+ *     exactly these sizes between guard bands with EVERY array 256-byte aligned, and no test hands
+ *     the library less.  Give them 256 bytes too.
  *
  * Parameter vector (`params`, `grad_params`): one flat fp32 vector holding the
  * three networks in the reference's state_dict order (models.py:343-352;
