@@ -11,6 +11,12 @@
  *                              :352-416 (CustomCollateFnGen, func_appl_X = power-k)
  *   njode_cond_exp_f64         stock_model.py:50-158 (compute_cond_exp, get_optimal_loss),
  *                              :178, :353, :393 (next_cond_exp), :471-481 (compute_loss)
+ *   njode_generate_stage       stock_model.py:288-335 (HestonWOFeller.generate_paths) and the
+ *                              three generators above started from start_X, as
+ *                              data_utils.py:111-195 (create_combined_dataset) chains them
+ *   njode_cond_exp_staged_f64  stock_model.py:421-466 (Combined.compute_cond_exp: stage i starts
+ *                              where stage i - 1 ended), :277-286 (HestonWOFeller.next_cond_exp
+ *                              with and without return_vol)
  *
  * Conventions are those of njode_hip.h (device pointers, caller-owned buffers, caller's
  * stream, int return code + njode_last_error()).
@@ -132,6 +138,64 @@ int njode_cond_exp_f64(const NjodeSde* sde, const NjodeBatch* batch,
                        const NjodeCondExpSchedule* sched, double weight, const float* pred,
                        double* path_y, double* opt_loss, double* sq_diff, void* ws,
                        size_t ws_bytes, njodeStream_t stream);
+
+/* ---- regime-switch datasets and Heston without the Feller condition ----------------------
+ * The entry points above keep their model set; the fourth model and the stage-by-stage forms
+ * arrive through the entry points below. */
+#define NJODE_SDE_HESTON_WO_FELLER 3
+#define NJODE_MAX_STAGES 16
+
+/* One stage of a regime-switch dataset, or a single model with the options of the fourth. */
+typedef struct NjodeSdeStage {
+  NjodeSde sde;        /* model: any NJODE_SDE_*; n_steps = S_i and maturity of THIS stage     */
+  double v0;           /* HestonWOFeller: variance at the stage's start (reference: mean)      */
+  int32_t return_vol;  /* HestonWOFeller: the variance is stored as coordinates dim .. 2 dim-1 */
+  int32_t first_step;  /* generation: s0, the grid index the stage starts at;
+                          conditional expectation: index of the stage's first Euler step      */
+} NjodeSdeStage;
+
+/* Euler-Maruyama paths of one stage into slices [s0 .. s0 + S_i] of paths_tm
+ * f64 [total_steps + 1][dim_out][N], dim_out = dim (return_vol: 2 dim).  s0 = 0: the stage starts
+ * from S0 and writes slice 0.  s0 > 0: the start values are READ from slice s0 (the previous
+ * stage's last slice), which is left untouched; the variance of Heston / HestonWOFeller starts
+ * afresh (mean / v0), as the reference's generators do.
+ * normals == NULL : Philox draws as in njode_generate_paths with the GLOBAL grid index s0 + k
+ *                   in the counter's step word (Black-Scholes / OrnsteinUhlenbeck: pair
+ *                   ceil((s0 + k) / 2), first normal at odd, second at even global index; a
+ *                   stage at an odd s0 takes the second normal of a pair first).
+ *                   periodic_coeff sees the stage-local time (k - 1) dt, dt = maturity / S_i.
+ * normals != NULL : the stage's own draws, [N][S_i][dim] (Heston, HestonWOFeller:
+ *                   [N][S_i][2][dim]).
+ * HestonWOFeller (float64, no fused multiply-adds, vp = max(v, 0) of the PREVIOUS variance):
+ *   s' = exp((log(s) + (drift pc - 0.5 vp) dt) + sqrt(vp) dW)
+ *   v' = (v + (-speed (vp - mean)) dt) + (volatility sqrt(vp)) dZ
+ * NJODE_E_BADARG: null or non-positive sizes, s0 < 0 or s0 + S_i > total_steps, an unknown
+ * model, correlation outside [-1, 1], return_vol with another model or with s0 > 0. */
+int njode_generate_stage(const NjodeSdeStage* stage, int32_t total_steps, uint64_t seed,
+                         const double* normals, double* paths_tm, njodeStream_t stream);
+
+/* workspace of one staged call, in bytes */
+int njode_cond_exp_staged_bytes(int32_t B, int32_t n_obs, int32_t n_times, int32_t n_steps,
+                                int32_t dim, int32_t n_stages, size_t* out);
+
+/* njode_cond_exp_f64 for a chain of stages (HOST array, 1 <= n_stages <= NJODE_MAX_STAGES):
+ * Euler step k takes the factors of the stage with the largest first_step <= k; the clock
+ * (schedule.cond_exp_clock with stage maturities) carries the partial step that ends a stage.
+ * step_t is the global clock: that is what a stage's periodic_coeff sees.  Of each stage
+ * sde.model, has_sine, sine_coeff, drift, mean, speed, return_vol and first_step are read; the
+ * width `dim` of the batch is stages[0].sde.dim.
+ * Factors per coordinate class: class 0  a = exp(rate pc(t) step), c = 0 (OrnsteinUhlenbeck:
+ * mean (1 - a)); class 1, the variance coordinates j >= dim / 2 of a return_vol stage:
+ * a = exp(-speed step), c = mean (1 - a), no periodic coefficient.
+ * Outputs, reductions and reproducibility as njode_cond_exp_f64; a single stage of one of its
+ * three models gives the same bits as that call.
+ * NJODE_E_BADARG: what njode_cond_exp_f64 refuses, n_stages outside [1, NJODE_MAX_STAGES],
+ * first_step not strictly increasing from 0 or beyond n_steps, return_vol with an odd dim, with
+ * another model or in a call of more than one stage, an unknown model. */
+int njode_cond_exp_staged_f64(const NjodeSdeStage* stages, int32_t n_stages,
+                              const NjodeBatch* batch, const NjodeCondExpSchedule* sched,
+                              double weight, const float* pred, double* path_y, double* opt_loss,
+                              double* sq_diff, void* ws, size_t ws_bytes, njodeStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -34,9 +34,14 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
            'njode_collate_count', 'njode_collate_fill',
            'njode_cond_exp_bytes', 'njode_cond_exp_f64',
+           'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
 SDE_MODELS = {'BlackScholes': 0, 'OrnsteinUhlenbeck': 1, 'Heston': 2}
+# (the fourth model is known to the staged entry points only: njode_generate_stage,
+# njode_cond_exp_staged_f64)
+SDE_MODELS_STAGED = dict(SDE_MODELS, HestonWOFeller=3)
+MAX_STAGES = 16     # NJODE_MAX_STAGES (include/njode_producer.h)
 
 
 MAX_HIDDEN = 8      # NJODE_MAX_HIDDEN (include/njode_hip.h)
@@ -75,6 +80,11 @@ class NjodeSde(C.Structure):
                 ('drift', C.c_double), ('volatility', C.c_double), ('mean', C.c_double),
                 ('speed', C.c_double), ('correlation', C.c_double), ('S0', C.c_double),
                 ('maturity', C.c_double), ('sine_coeff', C.c_double)]
+
+
+class NjodeSdeStage(C.Structure):
+    _fields_ = [('sde', NjodeSde), ('v0', C.c_double), ('return_vol', C.c_int32),
+                ('first_step', C.c_int32)]
 
 
 class NjodeCondExpSchedule(C.Structure):
@@ -156,9 +166,15 @@ def lib():
     L.njode_cond_exp_f64.argtypes = [C.POINTER(NjodeSde), C.POINTER(NjodeBatch),
                                      C.POINTER(NjodeCondExpSchedule), f64, vp, vp, vp, vp, vp, sz,
                                      vp]
+    L.njode_generate_stage.argtypes = [C.POINTER(NjodeSdeStage), i32, u64, vp, vp, vp]
+    L.njode_cond_exp_staged_bytes.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.njode_cond_exp_staged_f64.argtypes = [C.POINTER(NjodeSdeStage), i32, C.POINTER(NjodeBatch),
+                                            C.POINTER(NjodeCondExpSchedule), f64, vp, vp, vp, vp,
+                                            vp, sz, vp]
     for name in ('njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
                  'njode_collate_count', 'njode_collate_fill',
                  'njode_cond_exp_bytes', 'njode_cond_exp_f64',
+                 'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
         getattr(L, name).restype = C.c_int

@@ -138,6 +138,92 @@ __global__ void __launch_bounds__(256) k_generate(NjodeSde p, double dt, double 
   }
 }
 
+// One stage of a regime-switch dataset (njode_generate_stage): k_generate's recurrences from
+// slice s0 on.  The Philox counter carries the GLOBAL grid index g = s0 + k, periodic_coeff the
+// stage-local time; Black-Scholes / OrnsteinUhlenbeck take the first normal of pair (g + 1) / 2 at
+// odd g and the second at even g, so a stage that starts at an odd s0 draws the pair of its first
+// step again and takes the second.  HestonWOFeller with return_vol: the thread of (j, n) writes
+// its spot to coordinate j and its variance to coordinate dim + j.
+template <int MODEL>
+__global__ void __launch_bounds__(256) k_generate_stage(NjodeSde p, double v0, int return_vol,
+                                                        int s0, double dt, double sq, double rho_c,
+                                                        uint32_t seed_lo, uint32_t seed_hi,
+                                                        const double* __restrict__ normals,
+                                                        double* __restrict__ paths) {
+  constexpr bool TWO = MODEL == NJODE_SDE_HESTON || MODEL == NJODE_SDE_HESTON_WO_FELLER;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long N = p.n_paths;
+  if (tid >= N * p.dim) return;
+  const int j = (int)(tid / N);
+  const long long n = tid % N;
+  const int dim_out = return_vol ? 2 * p.dim : p.dim;
+  const size_t slice = (size_t)dim_out * N;
+  double* out = paths + (size_t)s0 * slice + (size_t)j * N + n;
+  double* out_v = out + (size_t)p.dim * N;     // (return_vol only)
+  double s, z_next = 0.0;
+  double v = MODEL == NJODE_SDE_HESTON_WO_FELLER ? v0 : p.mean;
+  if (s0 == 0) {
+    s = p.S0;
+    out[0] = s;
+    if (return_vol) out_v[0] = v;
+  } else {
+    s = out[0];
+  }
+  for (int k = 1; k <= p.n_steps; ++k) {
+    const uint32_t g = (uint32_t)(s0 + k);
+    double z1, z2;
+    if (normals) {
+      if (TWO) {
+        const size_t base = (((size_t)n * p.n_steps + (k - 1)) * 2) * p.dim + j;
+        z1 = normals[base];
+        z2 = normals[base + p.dim];
+      } else {
+        z1 = normals[((size_t)n * p.n_steps + (k - 1)) * p.dim + j];
+        z2 = 0.0;
+      }
+    } else if (TWO) {
+      const U4 r = philox4x32_10(U4{(uint32_t)n, (uint32_t)(n >> 32), g, (uint32_t)j}, seed_lo,
+                                 seed_hi ^ STREAM_PATHS);
+      normal_pair(r, z1, z2);
+    } else {
+      if ((g & 1u) || k == 1) {
+        const U4 r = philox4x32_10(U4{(uint32_t)n, (uint32_t)(n >> 32), (g + 1u) >> 1, (uint32_t)j},
+                                   seed_lo, seed_hi ^ STREAM_PATHS);
+        double first;
+        normal_pair(r, first, z_next);
+        z1 = (g & 1u) ? first : z_next;
+      } else {
+        z1 = z_next;
+      }
+      z2 = 0.0;
+    }
+    const double tk = (double)(k - 1) * dt;
+    const double pc = p.has_sine ? 1.0 + sin(p.sine_coeff * tk) : 1.0;
+    const double dW = z1 * sq;
+    if (MODEL == NJODE_SDE_BLACK_SCHOLES) {
+      const double mu = p.drift * pc * s;
+      const double sig = p.volatility * s;
+      s = (s + mu * dt) + sig * dW;
+    } else if (MODEL == NJODE_SDE_ORNSTEIN_UHLENBECK) {
+      const double mu = -p.speed * pc * (s - p.mean);
+      s = (s + mu * dt) + p.volatility * dW;
+    } else if (MODEL == NJODE_SDE_HESTON) {
+      const double dZ = (p.correlation * z1 + rho_c * z2) * sq;
+      const double vn = (v + (-p.speed * (v - p.mean)) * dt) + (p.volatility * sqrt(v)) * dZ;
+      s = (s + (p.drift * pc * s) * dt) + (sqrt(vn) * s) * dW;
+      v = vn;
+    } else {
+      const double dZ = (p.correlation * z1 + rho_c * z2) * sq;   // stock_model.py:314-328
+      const double vp = v > 0.0 ? v : 0.0;                        // np.maximum(v, 0)
+      const double rt = sqrt(vp);
+      s = exp((log(s) + (p.drift * pc - 0.5 * vp) * dt) + rt * dW);
+      v = (v + (-p.speed * (vp - p.mean)) * dt) + (p.volatility * rt) * dZ;
+    }
+    out[(size_t)k * slice] = s;
+    if (return_vol) out_v[(size_t)k * slice] = v;
+  }
+}
+
 // ---- observation mask -------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_sample_obs(int N, int S, double perc, uint32_t seed_lo,
                                                     uint32_t seed_hi,
@@ -303,6 +389,44 @@ extern "C" int njode_generate_paths(const NjodeSde* sde, uint64_t seed, const do
     default:
       return fail(NJODE_E_UNSUPPORTED, "unknown SDE model %d", sde->model);
   }
+  HIP_TRY(hipGetLastError());
+  return NJODE_OK;
+}
+
+extern "C" int njode_generate_stage(const NjodeSdeStage* stage, int32_t total_steps, uint64_t seed,
+                                    const double* normals, double* paths_tm,
+                                    njodeStream_t stream) {
+  if (!stage || !paths_tm) return fail(NJODE_E_BADARG, "null argument");
+  const NjodeSde* sde = &stage->sde;
+  const int s0 = stage->first_step;
+  if (sde->n_paths <= 0 || sde->dim <= 0 || sde->n_steps <= 0)
+    return fail(NJODE_E_BADARG, "n_paths, dim and n_steps must be positive");
+  if (s0 < 0 || total_steps < sde->n_steps || s0 > total_steps - sde->n_steps)
+    return fail(NJODE_E_BADARG, "the stage [%d, %d + %d] leaves the grid of %d steps", s0, s0,
+                sde->n_steps, total_steps);
+  if (sde->model < NJODE_SDE_BLACK_SCHOLES || sde->model > NJODE_SDE_HESTON_WO_FELLER)
+    return fail(NJODE_E_BADARG, "unknown SDE model %d", sde->model);
+  const bool two = sde->model == NJODE_SDE_HESTON || sde->model == NJODE_SDE_HESTON_WO_FELLER;
+  if (two && !(sde->correlation >= -1.0 && sde->correlation <= 1.0))
+    return fail(NJODE_E_BADARG, "correlation outside [-1, 1]");
+  const int rv = stage->return_vol != 0;
+  if (rv && (sde->model != NJODE_SDE_HESTON_WO_FELLER || s0 > 0))
+    return fail(NJODE_E_BADARG, "return_vol: HestonWOFeller from grid index 0 only");
+  const double dt = sde->maturity / sde->n_steps;
+  const double sq = __builtin_sqrt(dt);
+  const double rho_c = __builtin_sqrt(1.0 - sde->correlation * sde->correlation);
+  const int grid = cdiv((long long)sde->n_paths * sde->dim, 256);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+#define NJ_STAGE(M) \
+  k_generate_stage<M><<<grid, 256, 0, st>>>(*sde, stage->v0, rv, s0, dt, sq, rho_c, lo, hi, normals, paths_tm)
+  switch (sde->model) {
+    case NJODE_SDE_BLACK_SCHOLES: NJ_STAGE(NJODE_SDE_BLACK_SCHOLES); break;
+    case NJODE_SDE_ORNSTEIN_UHLENBECK: NJ_STAGE(NJODE_SDE_ORNSTEIN_UHLENBECK); break;
+    case NJODE_SDE_HESTON: NJ_STAGE(NJODE_SDE_HESTON); break;
+    default: NJ_STAGE(NJODE_SDE_HESTON_WO_FELLER); break;
+  }
+#undef NJ_STAGE
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
 }

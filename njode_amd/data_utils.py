@@ -9,6 +9,8 @@ that feeds the hot path:
 * ``hyperparam_default``            -- reference ``data_utils.py:25-31``
 * ``create_dataset`` (in memory)    -- reference ``data_utils.py:59-108``
   (RNG order: paths first, then the observation mask)
+* ``create_combined_dataset``       -- reference ``data_utils.py:111-195``
+  (regime switch: stage i starts at stage i - 1's last values)
 * ``save_dataset`` / ``load_dataset_dir`` -- the reference's on-disk layout
   ``data.npy`` (three consecutive ``np.save``) + ``metadata.txt``
   (``data_utils.py:98-105, 231-249``)
@@ -61,6 +63,44 @@ def create_dataset(stock_model_name="BlackScholes",
     nb_obs = np.sum(observed_dates[:, 1:], axis=1)
     hp['dt'] = dt
     return stock_paths, observed_dates, nb_obs, hp
+
+
+def create_combined_dataset(stock_model_names=("BlackScholes", "OrnsteinUhlenbeck"),
+                            hyperparam_dicts=(hyperparam_default, hyperparam_default),
+                            seed=0):
+    """Regime-switch dataset in memory (reference ``data_utils.py:111-195``): one
+    ``np.random.seed(seed)``, then every stage's ``generate_paths`` in turn -- stage ``i``
+    from the last values of stage ``i - 1`` -- and one uniform draw per (path, grid point) of
+    the concatenated grid, held to stage 0's ``obs_perc``.
+
+    :return: (stock_paths f64 [N, d, sum(S_i)+1], observed_dates, nb_obs, metadata with the
+              reference's keys, ``model_name='combined'``)
+    """
+    assert len(stock_model_names) == len(hyperparam_dicts)
+    hps = [copy.deepcopy(hp) for hp in hyperparam_dicts]
+    names = list(stock_model_names)
+    np.random.seed(seed=seed)
+    maturity = 0
+    stock_paths = last = dt = None
+    for i, (name, hp) in enumerate(zip(names, hps)):
+        if i:
+            assert hp['dimension'] == hps[i - 1]['dimension']
+            assert hp['nb_paths'] == hps[i - 1]['nb_paths']
+        maturity = maturity + hp['maturity']
+        hp['model_name'] = name
+        dt_last = dt
+        paths_i, dt = _STOCK_MODELS[name](**hp).generate_paths(start_X=last)
+        assert i == 0 or dt_last == dt
+        last = paths_i[:, :, -1]
+        stock_paths = paths_i if i == 0 else np.concatenate(
+            [stock_paths, paths_i[:, :, 1:]], axis=2)
+    n, _, s1 = stock_paths.shape
+    observed_dates = (np.random.random(size=(n, s1)) < hps[0]['obs_perc']) * 1
+    nb_obs = np.sum(observed_dates[:, 1:], axis=1)
+    metadata = {'dt': dt, 'maturity': maturity, 'dimension': hps[0]['dimension'],
+                'nb_paths': hps[0]['nb_paths'], 'model_name': 'combined',
+                'stock_model_names': names, 'hyperparam_dicts': hps}
+    return stock_paths, observed_dates, nb_obs, metadata
 
 
 def save_dataset(path, stock_paths, observed_dates, nb_obs, metadata):

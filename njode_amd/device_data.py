@@ -47,15 +47,15 @@ def parse_powers(func_names):
     return out
 
 
-def sde_struct(stock_model_name, hp, dim):
+def sde_struct(stock_model_name, hp, dim, models=_lib.SDE_MODELS):
     """``NjodeSde`` of a model name and its hyper-parameter dict (``create_dataset``'s
     ``hyperparam_dict`` / a dataset's metadata); vector-valued entries contribute their first
     component.  ``sine_<Model>`` names the same model (its ``sine_coeff`` is in the dict)."""
     name = stock_model_name[5:] if stock_model_name.startswith('sine_') else stock_model_name
-    if name not in _lib.SDE_MODELS:
+    if name not in models:
         raise ValueError('no analytic model named {!r}'.format(stock_model_name))
     sde = _lib.NjodeSde()
-    sde.model = _lib.SDE_MODELS[name]
+    sde.model = models[name]
     sde.n_paths, sde.dim, sde.n_steps = int(hp.get('nb_paths', 0)), int(dim), int(hp.get('nb_steps', 0))
     sc = hp.get('sine_coeff')
     sde.has_sine, sde.sine_coeff = (0, 0.0) if sc is None else (1, float(sc))
@@ -83,6 +83,55 @@ def _sde_of(sde, dim):
     return sde_struct(name, hp, dim)
 
 
+def stage_struct(stock_model_name, hp, dim, first_step=0):
+    """``NjodeSdeStage`` of the staged entry points: ``sde_struct`` with the fourth model,
+    ``return_vol`` and ``v0`` (default: ``mean``, as ``HestonWOFeller``'s constructor)."""
+    st = _lib.NjodeSdeStage()
+    st.sde = sde_struct(stock_model_name, hp, dim, _lib.SDE_MODELS_STAGED)
+    hwf = st.sde.model == _lib.SDE_MODELS_STAGED['HestonWOFeller']
+    st.return_vol = int(bool(hp.get('return_vol'))) if hwf else 0
+    v0 = hp.get('v0') if hwf else None
+    st.v0 = float(np.ravel(v0)[0]) if v0 is not None else st.sde.mean
+    st.first_step = int(first_step)
+    return st
+
+
+def _stages_of(sde, dim):
+    """What the staged entry point needs of a ``HestonWOFeller`` / ``Combined`` object or their
+    metadata: ``(list of NjodeSdeStage without first_step, stage maturities or None)``; None for
+    everything ``_sde_of`` describes.  ``ValueError``: inputs of another width (``return_vol``:
+    twice the model's dimensions), a combined description without stages, with more than
+    ``_lib.MAX_STAGES`` or with a ``return_vol`` stage."""
+    if isinstance(sde, dict):
+        name, hp = sde.get('model_name'), sde
+    else:
+        name = type(sde).__name__
+        hp = {k: getattr(sde, k, None) for k in _HP_KEYS + ('sine_coeff', 'return_vol', 'v0',
+                                                           'stock_model_names', 'hyperparam_dicts')}
+    if name in ('combined', 'Combined'):
+        names, hps = hp.get('stock_model_names'), hp.get('hyperparam_dicts')
+        if not names or hps is None or len(names) != len(hps):
+            raise ValueError('a combined description needs stock_model_names and as many hyperparam_dicts')
+        if len(names) > _lib.MAX_STAGES:
+            raise ValueError('at most {} stages'.format(_lib.MAX_STAGES))
+        stages = []
+        for n, h in zip(names, hps):
+            if h.get('return_vol') and n.endswith('HestonWOFeller'):
+                raise ValueError('a return_vol stage cannot be combined: its paths are twice as wide')
+            own = int(np.size(h.get('S0', 1)))
+            if own != dim:
+                raise ValueError('inputs are {} wide but stage {!r} has {} dimensions'.format(dim, n, own))
+            stages.append(stage_struct(n, h, dim))
+        return stages, [h['maturity'] for h in hps]
+    if name in ('HestonWOFeller', 'sine_HestonWOFeller'):
+        own = int(np.size(hp.get('S0', 1))) * (2 if hp.get('return_vol') else 1)
+        if own != dim:
+            raise ValueError('inputs are {} wide but the model stores {} coordinates (lifted inputs '
+                             'have no analytic conditional expectation)'.format(dim, own))
+        return [stage_struct('HestonWOFeller', hp, dim)], None
+    return None
+
+
 _ring = None
 
 
@@ -90,7 +139,10 @@ def cond_exp(sde, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot=Non
              pred=None, want_path=False, want_loss=False, M=None, start_time=None):
     """``StockModel.compute_cond_exp`` (``start_time=None``) on the GPU: the true conditional
     expectation of ``sde`` (a ``stock_model`` object or a dataset's metadata dict) along the
-    batch's schedule, in float64, and the metrics taken against it.  Returns
+    batch's schedule, in float64, and the metrics taken against it.  A ``Combined`` object or
+    ``'combined'`` metadata walks stage after stage as ``Combined.compute_cond_exp`` does (``T`` is
+    then the accumulated sum of the stages' maturities); ``HestonWOFeller`` with ``return_vol``
+    takes inputs ``2 d`` wide, the variance in the second half.  Returns
     ``(path_t, path_y, opt_loss, sq_diff)``:
 
     * ``path_t``  float64 numpy ``[n_t]`` -- the host walk's ``path_t``;
@@ -122,8 +174,17 @@ def cond_exp(sde, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot=Non
     B, dim = int(start_X.shape[0]), int(start_X.shape[1])
     if B == 0:
         raise ValueError('empty batch')
-    cs = _sde_of(sde, dim)
-    clock = cond_exp_clock(times, delta_t, T)
+    staged = _stages_of(sde, dim)
+    if staged is None:
+        cs = _sde_of(sde, dim)
+        clock = cond_exp_clock(times, delta_t, T)
+    else:
+        clock = cond_exp_clock(times, delta_t, T, staged[1])
+        if len(clock.stage_first) > 1 and np.any(np.diff(clock.stage_first) <= 0):
+            raise ValueError('a stage of the combined model has no Euler step on this clock')
+        cs = (_lib.NjodeSdeStage * len(staged[0]))(*staged[0])
+        for st, first in zip(cs, clock.stage_first):
+            st.first_step = int(first)
     tp = np.ascontiguousarray(time_ptr, dtype=np.int64).reshape(-1)
     n_obs = int(X.shape[0])
     if len(tp) != clock.n_times + 1 or tp[0] != 0 or tp[-1] != n_obs or np.any(np.diff(tp) < 0):
@@ -166,7 +227,10 @@ def cond_exp(sde, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot=Non
                             obs_idx.data_ptr() if n_obs else None,
                             n_obs_ot.data_ptr() if n_obs_ot is not None else None, float(B), 0, None)
     need = C.c_size_t(0)
-    _lib.check(L.njode_cond_exp_bytes(B, n_obs, nt, K, dim, C.byref(need)))
+    if staged is None:
+        _lib.check(L.njode_cond_exp_bytes(B, n_obs, nt, K, dim, C.byref(need)))
+    else:
+        _lib.check(L.njode_cond_exp_staged_bytes(B, n_obs, nt, K, dim, len(cs), C.byref(need)))
     ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
     path_y = torch.empty((n_t, B, dim), dtype=f64, device=dev) if want_path else None
     # (one allocation for both scalars: a caller that reads both fetches them in one copy)
@@ -176,9 +240,12 @@ def cond_exp(sde, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot=Non
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
         try:
-            _lib.check(L.njode_cond_exp_f64(
-                C.byref(cs), C.byref(batch), C.byref(sched), float(weight), _ptr(pred), _ptr(path_y),
-                _ptr(opt_loss), _ptr(sq_diff), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)))
+            tail = (C.byref(batch), C.byref(sched), float(weight), _ptr(pred), _ptr(path_y),
+                    _ptr(opt_loss), _ptr(sq_diff), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream))
+            if staged is None:
+                _lib.check(L.njode_cond_exp_f64(C.byref(cs), *tail))
+            else:
+                _lib.check(L.njode_cond_exp_staged_f64(cs, len(cs), *tail))
         finally:
             _ring.release_after(slot, stream)
     return clock.path_t.copy(), path_y, opt_loss, sq_diff
@@ -243,17 +310,22 @@ class DeviceDataset:
         for key in ('nb_paths', 'nb_steps'):
             if key not in hp:
                 raise KeyError(key)
-        if stock_model_name not in _lib.SDE_MODELS:   # (no 'sine_' aliases here: the name is stored)
+        if stock_model_name not in _lib.SDE_MODELS_STAGED:   # (no 'sine_' aliases here: the name is stored)
             raise KeyError(stock_model_name)
-        sde = sde_struct(stock_model_name, hp, dim)
+        hwf = stock_model_name == 'HestonWOFeller'
+        if hwf and hp.get('scheme', 'euler') != 'euler':
+            raise ValueError('unknown sampling scheme')
+        stage = stage_struct(stock_model_name, hp, dim)
+        sde = stage.sde
         N, S = sde.n_paths, sde.n_steps
-        paths = torch.empty((S + 1, dim, N), dtype=torch.float64, device=dev)
+        paths = torch.empty((S + 1, dim * (2 if stage.return_vol else 1), N), dtype=torch.float64,
+                            device=dev)
         observed = torch.empty((S + 1, N), dtype=torch.uint8, device=dev)
         nb_obs = torch.empty(N, dtype=torch.int32, device=dev)
         z = u = None
         if normals is not None:
             z = torch.as_tensor(np.ascontiguousarray(normals, dtype=np.float64)).to(dev)
-            per = 2 if stock_model_name == 'Heston' else 1
+            per = 2 if stock_model_name in ('Heston', 'HestonWOFeller') else 1
             if z.numel() != N * S * per * dim:
                 raise ValueError('normals must have N * S * {} * dim entries'.format(per))
         if uniforms is not None:
@@ -262,14 +334,87 @@ class DeviceDataset:
                 raise ValueError('uniforms must have N * (S + 1) entries')
         with torch.cuda.device(dev):
             st = _stream(dev)
-            _lib.check(L.njode_generate_paths(C.byref(sde), C.c_uint64(seed), _ptr(z), _ptr(paths),
-                                              st))
+            if hwf:
+                _lib.check(L.njode_generate_stage(C.byref(stage), S, C.c_uint64(seed), _ptr(z),
+                                                  _ptr(paths), st))
+            else:
+                _lib.check(L.njode_generate_paths(C.byref(sde), C.c_uint64(seed), _ptr(z),
+                                                  _ptr(paths), st))
             _lib.check(L.njode_sample_observations(N, S, float(hp['obs_perc']),
                                                    C.c_uint64(seed), _ptr(u), _ptr(observed),
                                                    _ptr(nb_obs), st))
         hp['dt'] = hp['maturity'] / hp['nb_steps']
         hp['model_name'] = stock_model_name
         return cls(paths, observed, nb_obs, hp)
+
+    @classmethod
+    def generate_combined(cls, stock_model_names, hyperparam_dicts, seed=0, device='cuda',
+                          normals=None, uniforms=None):
+        """``create_combined_dataset`` on the GPU: stage after stage into one buffer -- stage ``i``
+        reads its start values from the last slice of stage ``i - 1`` -- then one observation draw
+        over the concatenated grid with stage 0's ``obs_perc``; the reference's combined
+        metadata.  ``normals``: one array per stage (reference draw order) or None."""
+        L = _lib.lib()
+        dev = torch.device(device)
+        names = list(stock_model_names)
+        hps = [dict(hp) for hp in hyperparam_dicts]
+        if not names or len(names) != len(hps):
+            raise ValueError('one hyperparam_dict per stock model name, at least one')
+        if normals is not None and len(normals) != len(names):
+            raise ValueError('normals: one array per stage')
+        dim = int(np.size(hps[0].get('S0', 1)))
+        stages, s0 = [], 0
+        for i, (name, hp) in enumerate(zip(names, hps)):
+            for key in ('nb_paths', 'nb_steps'):
+                if key not in hp:
+                    raise KeyError(key)
+            if name not in _lib.SDE_MODELS_STAGED:
+                raise KeyError(name)
+            if name == 'HestonWOFeller' and hp.get('return_vol'):
+                raise ValueError('a return_vol stage cannot be combined: its paths are twice as wide')
+            if name == 'HestonWOFeller' and hp.get('scheme', 'euler') != 'euler':
+                raise ValueError('unknown sampling scheme')
+            if int(np.size(hp.get('S0', 1))) != dim or hp.get('dimension') != hps[0].get('dimension') \
+                    or hp['nb_paths'] != hps[0]['nb_paths']:
+                raise ValueError('stages must agree in dimension and nb_paths')
+            if dim != 1 and np.ptp(np.asarray(hp['S0'], dtype=np.float64)) != 0:
+                raise ValueError('S0 must be the same in every dimension')
+            if hp['maturity'] / hp['nb_steps'] != hps[0]['maturity'] / hps[0]['nb_steps']:
+                raise ValueError('stages must agree in dt')
+            stages.append(stage_struct(name, hp, dim, first_step=s0))
+            s0 += stages[-1].sde.n_steps
+            hp['model_name'] = name
+        N, S = stages[0].sde.n_paths, s0
+        paths = torch.empty((S + 1, dim, N), dtype=torch.float64, device=dev)
+        observed = torch.empty((S + 1, N), dtype=torch.uint8, device=dev)
+        nb_obs = torch.empty(N, dtype=torch.int32, device=dev)
+        zs = [None] * len(stages)
+        if normals is not None:
+            for i, (st, name) in enumerate(zip(stages, names)):
+                zs[i] = torch.as_tensor(np.ascontiguousarray(normals[i], dtype=np.float64)).to(dev)
+                per = 2 if name in ('Heston', 'HestonWOFeller') else 1
+                if zs[i].numel() != N * st.sde.n_steps * per * dim:
+                    raise ValueError('normals[{}] must have N * S_i * {} * dim entries'.format(i, per))
+        u = None
+        if uniforms is not None:
+            u = torch.as_tensor(np.ascontiguousarray(uniforms, dtype=np.float64)).to(dev)
+            if u.numel() != N * (S + 1):
+                raise ValueError('uniforms must have N * (S + 1) entries')
+        with torch.cuda.device(dev):
+            stream = _stream(dev)
+            for st, z in zip(stages, zs):
+                _lib.check(L.njode_generate_stage(C.byref(st), S, C.c_uint64(seed), _ptr(z),
+                                                  _ptr(paths), stream))
+            _lib.check(L.njode_sample_observations(N, S, float(hps[0]['obs_perc']),
+                                                   C.c_uint64(seed), _ptr(u), _ptr(observed),
+                                                   _ptr(nb_obs), stream))
+        maturity = 0
+        for hp in hps:
+            maturity = maturity + hp['maturity']
+        meta = {'dt': hps[-1]['maturity'] / hps[-1]['nb_steps'], 'maturity': maturity,
+                'dimension': hps[0].get('dimension'), 'nb_paths': hps[0]['nb_paths'],
+                'model_name': 'combined', 'stock_model_names': names, 'hyperparam_dicts': hps}
+        return cls(paths, observed, nb_obs, meta)
 
     @classmethod
     def from_arrays(cls, stock_paths, observed_dates, nb_obs, metadata, device='cuda'):

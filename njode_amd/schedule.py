@@ -94,19 +94,67 @@ class Schedule:
 
 
 CondExpClock = collections.namedtuple(
-    'CondExpClock', 'step_dt step_t k_jump path_t row_of_jump n_steps n_times')
+    'CondExpClock', 'step_dt step_t k_jump path_t row_of_jump n_steps n_times stage_first')
 
 
-def cond_exp_clock(times, delta_t, T):
+def _walk_clock_staged(times, delta_t, maturities):
+    """The clock of ``stock_model.Combined.compute_cond_exp``: the single walk's lists plus the
+    index of every stage's first Euler step.  Stage ``i`` walks to its accumulated ``T``; the next
+    one starts at the last clock value written (``path_t[-1]``: that ``T`` through a partial step,
+    or an observation time within 1e-10 of it) and passes over the times it has reached."""
+    dts, ts, k_jump, path_t, row_of_jump, stage_first = [], [], [], [0.0], [], []
+    now, T = 0.0, 0
+
+    def walk(now, target):
+        guard = target - 1e-10 * delta_t
+        while now < guard:
+            step = delta_t if now < target - delta_t else target - now
+            dts.append(step)
+            ts.append(now)
+            now = now + step
+            path_t.append(now)
+        return now
+
+    for si, maturity in enumerate(maturities):
+        T = T + maturity
+        if si:
+            now = path_t[-1]
+        stage_first.append(len(dts))
+        for obs_time in times:
+            if obs_time > T + 1e-10:
+                break
+            if obs_time <= now:
+                continue
+            now = walk(now, obs_time)
+            k_jump.append(len(dts))
+            row_of_jump.append(len(path_t))
+            path_t.append(obs_time)
+        now = walk(now, T)
+    return dts, ts, k_jump, path_t, row_of_jump, stage_first
+
+
+def cond_exp_clock(times, delta_t, T, stage_maturities=None):
     """The clock of ``stock_model.StockModel.compute_cond_exp`` (``start_time=None``) in float64:
     ``step_dt`` / ``step_t`` [K] (length of Euler step k, clock before it), ``k_jump`` [n_times]
     int32, and ``path_t`` -- the host walk's ``path_t``, entry for entry.  It is ``Schedule``'s
     clock up to ``T`` before the fp32 rounding: the analytic factors are
     ``exp(rate * periodic_coeff(step_t) * step_dt)`` in float64.
 
+    ``stage_maturities`` (a list, one entry per stage of a regime-switch dataset): the clock of
+    ``stock_model.Combined.compute_cond_exp`` instead, stage after stage; ``T`` is then the
+    accumulated sum of the list, whatever is passed.  ``stage_first`` [n_stages] int32 is the
+    index of each stage's first Euler step (``[0]`` for the single walk).
+
     ``ValueError`` unless ``times`` is strictly increasing with ``0 < times[i] <= T + 1e-10``
     (the host walk silently skips a time its clock has reached and stops at one beyond ``T``)."""
     times = np.asarray(times, dtype=np.float64).reshape(-1)
+    if stage_maturities is not None:
+        stage_maturities = [float(m) for m in stage_maturities]
+        if not stage_maturities or not all(np.isfinite(m) and m > 0 for m in stage_maturities):
+            raise ValueError('stage maturities must be positive and finite, at least one')
+        T = 0
+        for m in stage_maturities:      # (accumulated as Combined.compute_cond_exp does)
+            T = T + m
     delta_t, T = float(delta_t), float(T)
     if not (delta_t > 0 and np.isfinite(delta_t) and np.isfinite(T)):
         raise ValueError('delta_t must be positive and T finite')
@@ -116,10 +164,18 @@ def cond_exp_clock(times, delta_t, T):
         raise ValueError('observation times must be strictly increasing and positive')
     if times.size and times[-1] > T + 1e-10:
         raise ValueError('observation time {!r} beyond T = {!r}'.format(float(times[-1]), T))
-    dts, ts, k_jump, path_t, row_of_jump = _walk_clock(times, delta_t, T, True, strict=True)
+    if stage_maturities is None:
+        dts, ts, k_jump, path_t, row_of_jump = _walk_clock(times, delta_t, T, True, strict=True)
+        stage_first = [0]
+    else:
+        dts, ts, k_jump, path_t, row_of_jump, stage_first = _walk_clock_staged(
+            times, delta_t, stage_maturities)
+        if len(k_jump) != len(times):
+            raise ValueError('an observation time falls between two stages of the clock')
     return CondExpClock(np.asarray(dts, dtype=np.float64), np.asarray(ts, dtype=np.float64),
                         np.asarray(k_jump, dtype=np.int32), np.asarray(path_t, dtype=np.float64),
-                        np.asarray(row_of_jump, dtype=np.int64), len(dts), len(times))
+                        np.asarray(row_of_jump, dtype=np.int64), len(dts), len(times),
+                        np.asarray(stage_first, dtype=np.int32))
 
 
 class ScheduleCache:

@@ -9,6 +9,8 @@ return conventions) for the models BASELINE.json's configs use:
 * ``BlackScholes``      -- reference ``stock_model.py:339-375``
 * ``OrnsteinUhlenbeck`` -- reference ``stock_model.py:378-418``
 * ``Heston``            -- reference ``stock_model.py:161-221``
+* ``HestonWOFeller``    -- reference ``stock_model.py:250-335``
+* ``Combined``          -- reference ``stock_model.py:421-466`` (regime switch)
 * ``compute_cond_exp``  -- reference ``stock_model.py:50-151``
 * ``compute_loss``      -- reference ``stock_model.py:471-481``
 
@@ -20,7 +22,8 @@ exactly the reference's order, so ``np.random.seed(s)`` followed by
 
 Deliberate difference: the reference's tail loop (``stock_model.py:139``) calls
 ``next_cond_exp(y, delta_t_)`` without ``current_t`` and raises ``TypeError``
-whenever the last observation time is < T.  Here the current time is passed.
+whenever the last observation time is < T.  Here the current time is passed
+(inside every stage of ``Combined`` too).
 """
 import copy
 
@@ -233,6 +236,103 @@ class Heston(StockModel):
         return spot, dt
 
 
+class HestonWOFeller(StockModel):
+    """Heston model that may violate the Feller condition ``2 speed mean > volatility**2``
+    (reference ``stock_model.py:250-335``): log-Euler spot driven by the *previous* variance,
+    the variance clamped at 0 wherever it is read.  ``return_vol=True`` appends the variance
+    paths along the dimension axis (the dataset is ``2 d`` wide)."""
+
+    def __init__(self, drift, volatility, mean, speed, correlation, nb_paths,
+                 nb_steps, S0, maturity, scheme='euler', return_vol=False,
+                 v0=None, sine_coeff=None, **kwargs):
+        super().__init__(drift=drift, volatility=volatility, nb_paths=nb_paths,
+                         nb_steps=nb_steps, S0=S0, maturity=maturity,
+                         sine_coeff=sine_coeff)
+        self.mean = mean
+        self.speed = speed
+        self.correlation = correlation
+        self.scheme = scheme
+        self.return_vol = return_vol
+        self.v0 = self.mean if v0 is None else v0
+
+    def next_cond_exp(self, y, delta_t, current_t):
+        growth = np.exp(self.drift * self.periodic_coeff(current_t) * delta_t)
+        if not self.return_vol:
+            return y * growth
+        s, v = np.split(y, indices_or_sections=2, axis=1)
+        s = s * growth
+        decay = np.exp(-self.speed * delta_t)     # (no periodic coefficient here)
+        v = v * decay + self.mean * (1 - decay)
+        return np.concatenate([s, v], axis=1)
+
+    def generate_paths(self, start_X=None):
+        if self.scheme != 'euler':
+            raise ValueError('unknown sampling scheme')
+        dt = self.maturity / self.nb_steps
+        spot = self._init_paths(start_X)
+        var = np.empty_like(spot)
+        var[:, :, 0] = self.v0
+        z = np.random.normal(0, 1, (self.nb_paths, self.nb_steps, 2,
+                                    self.dimensions))
+        sq = np.sqrt(dt)
+        rho = self.correlation
+        for k in range(1, self.nb_steps + 1):
+            z1 = z[:, k - 1, 0, :]
+            z2 = z[:, k - 1, 1, :]
+            dW = z1 * sq
+            dZ = (rho * z1 + np.sqrt(1 - rho ** 2) * z2) * sq
+            v_pos = np.maximum(var[:, :, k - 1], 0)
+            spot[:, :, k] = np.exp(
+                np.log(spot[:, :, k - 1])
+                + (self.drift * self.periodic_coeff((k - 1) * dt) - 0.5 * v_pos) * dt
+                + np.sqrt(v_pos) * dW)
+            var[:, :, k] = (var[:, :, k - 1] + (-self.speed * (v_pos - self.mean)) * dt
+                            + (self.volatility * np.sqrt(v_pos)) * dZ)
+        if self.return_vol:
+            spot = np.concatenate([spot, var], axis=1)
+        return spot, dt
+
+
+class Combined(StockModel):
+    """Regime switch (reference ``stock_model.py:421-466``): stage ``i`` of the conditional
+    expectation starts where stage ``i - 1`` ended, with ``T`` accumulated over the stages'
+    maturities; every stage's periodic coefficient sees the global clock."""
+
+    def __init__(self, stock_model_names, hyperparam_dicts, **kwargs):
+        self.stock_model_names = stock_model_names
+        self.hyperparam_dicts = hyperparam_dicts
+
+    def compute_cond_exp(self, times, time_ptr, X, obs_idx, delta_t, T, start_X,
+                         n_obs_ot, return_path=True, get_loss=False,
+                         weight=0.5, **kwargs):
+        T = 0
+        loss = 0
+        path_t = path_y = None
+        for i, name in enumerate(self.stock_model_names):
+            stage = STOCK_MODELS[name](**self.hyperparam_dicts[i])
+            T = T + self.hyperparam_dicts[i]['maturity']
+            _loss, _path_t, _path_y = stage.compute_cond_exp(
+                times, time_ptr, X, obs_idx, delta_t, T,
+                start_X if i == 0 else path_y[-1, :, :], n_obs_ot,
+                return_path=True, get_loss=get_loss, weight=weight,
+                start_time=None if i == 0 else path_t[-1])
+            loss = loss + _loss
+            if i == 0:
+                path_t, path_y = _path_t, _path_y
+            elif len(_path_t):
+                path_t = np.concatenate([path_t, _path_t])
+                path_y = np.concatenate([path_y, _path_y], axis=0)
+        if return_path:
+            return loss, np.array(path_t), np.array(path_y)
+        return loss
+
+    def get_optimal_loss(self, times, time_ptr, X, obs_idx, delta_t, T, start_X,
+                         n_obs_ot, weight=0.5):
+        return self.compute_cond_exp(
+            times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot,
+            return_path=False, get_loss=True, weight=weight)
+
+
 def compute_loss(X_obs, Y_obs, Y_obs_bj, n_obs_ot, batch_size, eps=1e-10,
                  weight=0.5):
     """Paper loss in numpy (reference ``stock_model.py:471-481``)."""
@@ -249,4 +349,6 @@ STOCK_MODELS = {
     "sine_BlackScholes": BlackScholes,
     "sine_Heston": Heston,
     "sine_OrnsteinUhlenbeck": OrnsteinUhlenbeck,
+    "HestonWOFeller": HestonWOFeller,
+    "combined": Combined,
 }
