@@ -4,10 +4,13 @@
 // forward / adjoint sweep of njode_chain.h) with
 //   -DNJ_ID=.. -DNJ_D=.. -DNJ_H=.. -DNJ_DO=.. -DNJ_NH=.. -DNJ_W=.. -DNJ_ACT=..
 //   -DNJ_MASKED=.. -DNJ_CURT=.. -DNJ_RES=.. -DNJ_PART=..
-#include <cstdlib>
-#include <cstring>
+// Every launcher here takes the call's Route (njode_route.h) and switches on it: which kernel runs is
+// decided there, once, and nothing in this file reads a switch or derives a route of its own.  Launch
+// errors: the helpers return nothing; HIP keeps the last error of the thread until it is read, and the
+// one hipGetLastError() at the end of each entry point (njode_seg_forward_ ...) reads it.
+#include <type_traits>
 
-#include "njode_host.h"
+#include "njode_route.h"
 #if NJ_PART >= 4
 #include "njode_chain.h"
 #include "njode_chain_seg.h"
@@ -25,11 +28,8 @@ namespace njode {
 using C = Cfg<NJ_D, NJ_H, NJ_DO, NJ_NH, NJ_W, NJ_ACT, (NJ_MASKED != 0), (NJ_CURT != 0),
               (NJ_RES != 0), (NJ_RNN != 0)>;
 
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-hipError_t NJ_CAT(njode_seg_forward_, NJ_ID)(const KArgs& a, bool drop, bool tails, int ode,
-                                            hipStream_t st);
-hipError_t NJ_CAT(njode_seg_backward_, NJ_ID)(const KArgs& a, bool drop, int ode, hipStream_t st);
+hipError_t NJ_CAT(njode_seg_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+hipError_t NJ_CAT(njode_seg_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
 constexpr bool HAS_MFMA = C::NH == 2 && !C::MASKED && !C::RNN && C::DO <= 16 && C::W < 64;
 // the lockstep forward on the matrix cores also covers masked shapes
 constexpr bool HAS_MFMA_LOCK = C::NH == 2 && !C::RNN && C::W < 64 && C::H <= 64 && C::DO <= 64;
@@ -37,29 +37,35 @@ constexpr bool HAS_MFMA_LOCK = C::NH == 2 && !C::RNN && C::W < 64 && C::H <= 64 
 constexpr bool HAS_MFMA_SWEEP =
     HAS_MFMA_LOCK && (!C::MASKED || C::ENC_CASE == 0 || (C::ENC_CASE == 1 && C::D == C::H));
 constexpr bool HAS_SPLIT = HAS_MFMA && SplitOk<C>::value;
-// masked shapes: one tile over the four waves of a block (njode_mfma_lock4.h); NJODE_LOCK4=0
-// keeps the one-wave kernels (maintainer A/B)
+// masked shapes: one tile over the four waves of a block (njode_mfma_lock4.h; Route: LOCK_TILE4)
 constexpr bool HAS_Q4 = HAS_MFMA_SWEEP && Q4Ok<C>::value;
-// ... or, for small batches, one wave per path (njode_chain.h; the choice is KArgs::chain, made by
-// njode_api.hip's make_layout)
+// ... or one wave per path (njode_chain.h; Route: LOCK_CHAIN)
 constexpr bool HAS_CHAIN = HAS_Q4 && ChainOk<C>::value;
-hipError_t NJ_CAT(njode_chain_forward_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st);
-hipError_t NJ_CAT(njode_chain_sweep_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st);
-// dW of the ODE network from the wave-per-chain sweeps' records (njode_chain_dw.h; part 5); false: not
-// launched (no stored deltas / segment sums for this call) -- k_ode_dw_pairs_mfma then
-bool NJ_CAT(njode_chain_dw_, NJ_ID)(const KArgs& a, hipStream_t st);
-// ... the same with the segment plan's encoder pass (k_encode_rows_bwd_mfma) as a role of the launch
-bool NJ_CAT(njode_chain_dw_enc_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st);
-// the segment plan's ODE kernels with one wave per item (njode_chain_seg.h; KArgs::seg_chain)
+void NJ_CAT(njode_chain_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+void NJ_CAT(njode_chain_sweep_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+// dW of the ODE network from the wave-per-chain sweeps' records (njode_chain_dw.h; part 5; Route::dw_stored)
+void NJ_CAT(njode_chain_dw_, NJ_ID)(const KArgs& a, hipStream_t st);
+// the segment plan's ODE kernels with one wave per item (njode_chain_seg.h; Route::seg_chain)
 constexpr bool HAS_SEG_CHAIN = HAS_SPLIT && HAS_MFMA_SWEEP && SegChainOk<C>::value;
-hipError_t NJ_CAT(njode_seg_chain_forward_, NJ_ID)(const KArgs& a, bool drop, bool tails, hipStream_t st);
-hipError_t NJ_CAT(njode_seg_chain_backward_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st);
-static inline bool lock4_on() {
-  static const bool on = [] {
-    const char* e = getenv("NJODE_LOCK4");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+void NJ_CAT(njode_seg_chain_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+void NJ_CAT(njode_seg_chain_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+
+// f(std::true_type) when the call draws dropout masks, else f(std::false_type): the kernels take it as a
+// template argument
+template <class F> static auto with_drop(bool drop, F f) {
+  return drop ? f(std::true_type{}) : f(std::false_type{});
+}
+// Profile scope names of the ODE kernels a route runs: the launched kernels', as rocprofv3 lists them
+static inline const char* seg_fwd_name(const Route& r, bool tails) {
+  if (r.seg_ode != ODE_MFMA) return tails ? "k_ode_fwd_items.tails" : "k_ode_fwd_items";
+  if (r.seg_chain) return "k_seg_fwd_chain";   // (the tails ride)
+  if (r.ode_split) return tails ? "k_ode_fwd_split.tails" : "k_ode_fwd_mixed";
+  return tails ? "k_ode_fwd_mfma.tails" : "k_ode_fwd_mfma";
+}
+static inline const char* lock_name(int kind, bool bwd) {
+  if (kind == LOCK_VALU) return bwd ? "k_paths_bwd_adj" : "k_paths_fwd";
+  if (kind == LOCK_CHAIN) return bwd ? "k_paths_bwd_adj_chain" : "k_paths_fwd_chain";
+  return bwd ? "k_paths_bwd_adj_mfma" : "k_paths_fwd_mfma";
 }
 template <bool ON, class CC> struct FragSize {
   static constexpr int ode = 0, enc = 0, dec = 0;
@@ -141,15 +147,26 @@ template <class CC> static void launch_pack_frags(const KArgs& a, hipStream_t st
     }
   }
 }
-template <class CC, bool DROP> static void launch_mfma_enc(const KArgs& a, hipStream_t st) {
+template <class CC, bool DROP> static void launch_mfma_enc(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_MFMA) {
     const int n_tiles = cdiv(a.n_obs + a.B, 16);
     // one-wave blocks, 64 VGPRs: four waves per SIMD hide the row gathers (obs_idx -> path,
     // t_of_row -> k_jump, X) each tile starts with: 51 -> 37 us for 219 470 rows (the step time
     // does not move: the plan on the helper stream is the critical path beside this kernel);
-    // NJODE_ENC_BLOCKS overrides (A/B)
-    static const int enc_blocks = getenv("NJODE_ENC_BLOCKS") ? atoi(getenv("NJODE_ENC_BLOCKS")) : 4096;
-    k_encode_rows_mfma<CC, DROP><<<n_tiles < enc_blocks ? n_tiles : enc_blocks, 64, 0, st>>>(a);
+    // Route::enc_blocks: 4 096, NJODE_ENC_BLOCKS overrides (A/B)
+    k_encode_rows_mfma<CC, DROP><<<n_tiles < r.enc_blocks ? n_tiles : r.enc_blocks, 64, 0, st>>>(a);
+  }
+}
+// the three fragment tables of the lockstep plan's matrix-core kernels (parts 2 and 3)
+template <class CC> static void lock_pack_frags(const KArgs& a, hipStream_t st) {
+  if constexpr (HAS_MFMA_LOCK) {
+    using ES = typename EncS<CC>::type;
+    using DS = typename DecS<CC>::type;
+    k_pack_frags<CC><<<cdiv(MF<CC>::NALL * 64, 256), 256, 0, st>>>(a.P, a.frag);
+    k_pack_net<typename CC::Enc, ES><<<cdiv(ES::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_ENC,
+                                                                             a.frag_enc);
+    k_pack_net<typename CC::Dec, DS><<<cdiv(DS::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_DEC,
+                                                                             a.frag_dec);
   }
 }
 template <class CC, bool DROP> static void launch_mfma_jump(const KArgs& a, hipStream_t st) {
@@ -158,12 +175,12 @@ template <class CC, bool DROP> static void launch_mfma_jump(const KArgs& a, hipS
     k_jump_rows_mfma<CC, DROP><<<n_tiles < 2048 ? n_tiles : 2048, 64, 0, st>>>(a);
   }
 }
-template <class CC, bool DROP> static void launch_ode_bwd_mfma(const KArgs& a, bool split, hipStream_t st) {
+template <class CC, bool DROP> static void launch_ode_bwd_mfma(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_MFMA) {
     if constexpr (HAS_SPLIT) {
-      if (split) {
+      if (r.ode_split) {
         ProfScope ps("k_ode_bwd_mixed", st);
-        if (a.tile_q_on) k_ode_bwd_mixed<CC, DROP, true><<<a.n_blocks_bwd, 256, 0, st>>>(a);
+        if (r.tile_q_on) k_ode_bwd_mixed<CC, DROP, true><<<a.n_blocks_bwd, 256, 0, st>>>(a);
         else k_ode_bwd_mixed<CC, DROP, false><<<a.n_blocks_bwd, 256, 0, st>>>(a);
         return;
       }
@@ -179,35 +196,29 @@ template <class CC, bool DROP> static void launch_jump_rows_bwd(const KArgs& a, 
   }
 }
 template <class CC, bool DROP>
-static void launch_mfma_rows_bwd(const KArgs& a, bool split, hipStream_t st) {
+static void launch_mfma_rows_bwd(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_MFMA) {
     // (defer_loss == 2, NJODE_C_ROWS_IN_FWD: the forward call already ran this pass)
-    if (a.defer_loss != 2) launch_jump_rows_bwd<CC, DROP>(a, st);
-    bool enc_done = false;
-    if (HAS_SEG_CHAIN && a.seg_chain) enc_done = NJ_CAT(njode_seg_chain_backward_, NJ_ID)(a, DROP, st) == hipSuccess && a.dw_enc_fused;
-    else launch_ode_bwd_mfma<CC, DROP>(a, split, st);
-    if (!enc_done) {
+    if (r.defer_loss != 2) launch_jump_rows_bwd<CC, DROP>(a, st);
+    if (r.seg_chain) NJ_CAT(njode_seg_chain_backward_, NJ_ID)(a, r, st);
+    else launch_ode_bwd_mfma<CC, DROP>(a, r, st);
+    if (!r.dw_enc_fused) {   // (else a role of k_ode_dw_stored_enc's launch)
       ProfScope ps("k_encode_rows_bwd_mfma", st);
       k_encode_rows_bwd_mfma<CC, DROP><<<a.n_waves_rows / 4, 256, 0, st>>>(a);
     }
   }
 }
 template <class CC, bool DROP, bool TAIL>
-static void launch_mfma_fwd(const KArgs& a, bool split, hipStream_t st) {
+static void launch_mfma_fwd(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_MFMA) {
     const int n_tiles = cdiv(TAIL ? a.B : a.n_obs, 16);
     if constexpr (HAS_SPLIT) {
-      if (split) {
+      if (r.ode_split) {
         if constexpr (TAIL) {
-          // (the four-wave form for every plan.  NJODE_TAILS=single: one wave per tile on the
-          // scaled fragments for large plans, k_ode_fwd_tails -- measured beside the items' forward
-          // on the autograd route and slower, 1.121 against 1.075 ms per step: 4 096 one-wave blocks
-          // queue behind the forward's, the 1 024 four-wave blocks finish their tiles sooner)
-          static const bool tails_single = getenv("NJODE_TAILS") && strcmp(getenv("NJODE_TAILS"), "single") == 0;
-          if (n_tiles <= 768 || !tails_single)
-            k_ode_fwd_split<CC, DROP, true><<<n_tiles < 1024 ? n_tiles : 1024, 256, 0, st>>>(a);
-          else
-            k_ode_fwd_tails<CC, DROP><<<n_tiles < 4096 ? n_tiles : 4096, 64, 0, st>>>(a);
+          // (the four-wave form for every plan: one wave per tile for the large ones was measured
+          // beside the items' forward on the autograd route and slower, 1.121 against 1.075 ms per
+          // step -- profiles/r05_rejected_experiments.txt, item 2)
+          k_ode_fwd_split<CC, DROP, true><<<n_tiles < 1024 ? n_tiles : 1024, 256, 0, st>>>(a);
         }
         else if (a.plan_job) {
           // the next batch's plan rides in front of this launch's own blocks (njode_plan.h)
@@ -216,7 +227,7 @@ static void launch_mfma_fwd(const KArgs& a, bool split, hipStream_t st) {
           // limit once it carries the plan; njode_api.hip launches the plan in front of such a call)
           k_ode_fwd_mixed_plan<CC, DROP, false><<<a.n_blocks_fwd + job.P, 256, 0, st>>>(a, job);
         }
-        else if (a.enc_fused) k_ode_fwd_mixed<CC, DROP, true><<<a.n_blocks_fwd, 256, 0, st>>>(a);
+        else if (r.enc_fused) k_ode_fwd_mixed<CC, DROP, true><<<a.n_blocks_fwd, 256, 0, st>>>(a);
         else k_ode_fwd_mixed<CC, DROP, false><<<a.n_blocks_fwd, 256, 0, st>>>(a);
         return;
       }
@@ -225,15 +236,14 @@ static void launch_mfma_fwd(const KArgs& a, bool split, hipStream_t st) {
   }
 }
 
-hipError_t NJ_CAT(njode_lock_forward_, NJ_ID)(const KArgs& a, bool drop, bool path, bool loss, int ode,
-                                             hipStream_t st);
-hipError_t NJ_CAT(njode_lock_backward_, NJ_ID)(const KArgs& a, bool drop, int ode, hipStream_t st);
+hipError_t NJ_CAT(njode_lock_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
+hipError_t NJ_CAT(njode_lock_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st);
 
 #if NJ_PART == 0
-template <bool DROP, bool TAIL, int ODE> static void launch_ode_fwd(const KArgs& a, hipStream_t st) {
+template <bool DROP, bool TAIL, int ODE> static void launch_ode_fwd(const KArgs& a, const Route& r, hipStream_t st) {
   const int n_items = TAIL ? a.B : a.n_obs;
   if constexpr (ODE == ODE_MFMA) {
-    launch_mfma_fwd<C, DROP, TAIL>(a, a.ode_split != 0, st);
+    launch_mfma_fwd<C, DROP, TAIL>(a, r, st);
   } else {
     constexpr bool WLDS = ODE == ODE_VALU_LDS;
     constexpr int NT = WLDS ? 256 : 64;
@@ -241,39 +251,28 @@ template <bool DROP, bool TAIL, int ODE> static void launch_ode_fwd(const KArgs&
   }
 }
 template <bool DROP, int ODE>
-static hipError_t seg_forward_t(const KArgs& a, bool tails, hipStream_t st) {
+static hipError_t seg_forward_t(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (C::MASKED || C::RNN) {
     return hipErrorNotSupported;
   } else {
     // pack + encoder rows: on the call's helper stream when there is one (they only need
     // t_of_row; the plan kernels already sit on `st`), else in line
-    const SideInfo* side = (const SideInfo*)a.plan_ready;
+    const SideInfo* side = r.side ? (const SideInfo*)a.plan_ready : nullptr;
     hipStream_t s2 = side ? side->st : st;
     if (side) (void)hipStreamWaitEvent(s2, side->e0, 0);
-    // (a copy of the arguments: whether the keep bits are drawn ahead is decided here)
-    KArgs ab = a;
+    KArgs ab = a;   // (a copy of the arguments: dbits_ready, plan_sync_zero)
     if constexpr (ODE == ODE_MFMA) {
-      static const bool bits_off = getenv("NJODE_DROP_BITS_AHEAD") && atoi(getenv("NJODE_DROP_BITS_AHEAD")) == 0;
-      // (plans whose every tile runs four waves wide, i.e. small batches: there the forward IS the
-      // chain of its longest tile; in the mixed kernel of a large plan the four-wave blocks are
-      // ~10 % of the work and the extra blocks of this launch cost more than they save:
-      // 20 000 paths, k_pack_all 7.5 -> 12.3 us for ~1.5 us off k_ode_fwd_mixed)
-      // ... and the wave-per-item forward's lane masks (they need nothing of the plan: any stream)
-      const bool bits = a.seg_chain ? (DROP && a.dbits != nullptr)
-                                    : (DROP && HAS_SPLIT && a.ode_split && a.dbits && !side && !bits_off &&
-                                       a.n_split_fwd == a.n_blocks_fwd);
-      ab.dbits_ready = bits ? 1 : 0;
+      ab.dbits_ready = r.seg_bits_ahead ? 1 : 0;
       if (ab.plan_sync_zero && s2 != st) {   // (the pack launch is not on the hosting launch's stream)
         (void)hipMemsetAsync(ab.plan_sync_zero, 0, 8 * sizeof(unsigned), st);
         ab.plan_sync_zero = nullptr;
       }
       ProfScope ps("k_pack_all", s2);
-      launch_pack_frags<C>(ab, s2, bits);
+      launch_pack_frags<C>(ab, s2, r.seg_bits_ahead);
     }
-    const bool enc_fused = ODE == ODE_MFMA && HAS_SPLIT && a.enc_fused != 0;
-    if (!enc_fused) {
+    if (!r.enc_fused) {
       ProfScope ps(ODE == ODE_MFMA ? "k_encode_rows_mfma" : "k_encode_rows", s2);
-      if constexpr (ODE == ODE_MFMA) launch_mfma_enc<C, DROP>(a, s2);
+      if constexpr (ODE == ODE_MFMA) launch_mfma_enc<C, DROP>(a, r, s2);
       else k_encode_rows<C, DROP><<<cdiv(a.n_obs + a.B, 64), 64, 0, s2>>>(a);
     }
     if (side) {
@@ -281,7 +280,7 @@ static hipError_t seg_forward_t(const KArgs& a, bool tails, hipStream_t st) {
       (void)hipStreamWaitEvent(st, side->e1, 0);
     }
     if constexpr (ODE == ODE_MFMA && HAS_SPLIT) {
-      if (enc_fused) {
+      if (r.enc_fused) {
         // NJODE_ENC_FUSED: what the ODE forward's one-wave role does not evaluate itself (needs the
         // plan -- the item order and the split point -- so it runs on `st`, behind it)
         ProfScope ps("k_encode_rows_items", st);
@@ -292,9 +291,7 @@ static hipError_t seg_forward_t(const KArgs& a, bool tails, hipStream_t st) {
     // the tails (hT: every path from its last observation to the end) need the encoder's outputs
     // and nothing else of this call: with helper streams they start TOGETHER with the items' ODE
     // forward, on a stream of their own, and share the chip with it
-    const bool chain = HAS_SEG_CHAIN && ODE == ODE_MFMA && a.seg_chain != 0;   // (tails ride in its launch)
-    const bool tails_side = tails && side != nullptr && !chain;
-    if (tails_side) {
+    if (r.tails_side) {
       // the tails' stream waits for the encoder rows and for the plan's tail order: the latter is
       // on that stream itself (njode_api.hip, build_plan) or, failing that, on `st` -- then e0,
       // which the helper stream consumed above, is recorded again here to stand for "everything
@@ -305,50 +302,42 @@ static hipError_t seg_forward_t(const KArgs& a, bool tails, hipStream_t st) {
         (void)hipStreamWaitEvent(side->st2, side->e0, 0);
       }
     }
-    if (chain) {
-      ProfScope ps("k_seg_fwd_chain", st);
-      (void)NJ_CAT(njode_seg_chain_forward_, NJ_ID)(ab, DROP, tails, st);
-    } else {   // (the names are the launched kernels', as rocprofv3 lists them)
-      ProfScope ps(ODE == ODE_MFMA ? (HAS_SPLIT && a.ode_split ? "k_ode_fwd_mixed" : "k_ode_fwd_mfma")
-                                   : "k_ode_fwd_items", st);
-      launch_ode_fwd<DROP, false, ODE>(ab, st);
+    {
+      ProfScope ps(seg_fwd_name(r, false), st);
+      if (r.seg_chain) NJ_CAT(njode_seg_chain_forward_, NJ_ID)(ab, r, st);
+      else launch_ode_fwd<DROP, false, ODE>(ab, r, st);
     }
-    if (chain) {
-    } else if (tails_side) {
+    if (r.tails_side) {
       // (queued behind the forward's launch only so that the items' kernel is dispatched first)
-      ProfScope ps(ODE == ODE_MFMA ? (HAS_SPLIT && a.ode_split ? "k_ode_fwd_split.tails" : "k_ode_fwd_mfma.tails")
-                                   : "k_ode_fwd_items.tails", side->st2);
-      launch_ode_fwd<DROP, true, ODE>(a, side->st2);
+      ProfScope ps(seg_fwd_name(r, true), side->st2);
+      launch_ode_fwd<DROP, true, ODE>(a, r, side->st2);
       (void)hipEventRecord(side->e2, side->st2);
-    } else if (tails) {
-      ProfScope ps(ODE == ODE_MFMA ? (HAS_SPLIT && a.ode_split ? "k_ode_fwd_split.tails" : "k_ode_fwd_mfma.tails")
-                                   : "k_ode_fwd_items.tails", st);
-      launch_ode_fwd<DROP, true, ODE>(a, st);
+    } else if (r.tails && !r.tails_ride) {
+      ProfScope ps(seg_fwd_name(r, true), st);
+      launch_ode_fwd<DROP, true, ODE>(a, r, st);
     }
-    if (ODE == ODE_MFMA && a.defer_loss == 2) {
+    if (r.defer_loss == 2) {
       // NJODE_C_ROWS_IN_FWD: the backward's row pass here (loss terms, readout gradients, adjoints
       // at the segment ends) instead of the forward-only pass
       launch_jump_rows_bwd<C, DROP>(a, st);
-    } else if (!(ODE == ODE_MFMA && a.defer_loss)) {
+    } else if (!r.defer_loss) {
       ProfScope ps(ODE == ODE_MFMA ? "k_jump_rows_mfma" : "k_jump_rows", st);
       if constexpr (ODE == ODE_MFMA) launch_mfma_jump<C, DROP>(a, st);
       else k_jump_rows<C, DROP><<<cdiv(a.n_obs, 64), 64, 0, st>>>(a);
     }
-    if (tails_side) (void)hipStreamWaitEvent(st, side->e2, 0);
+    if (r.tails_side) (void)hipStreamWaitEvent(st, side->e2, 0);
     return hipGetLastError();
   }
 }
-hipError_t NJ_CAT(njode_seg_forward_, NJ_ID)(const KArgs& a, bool drop, bool tails, int ode,
-                                            hipStream_t st) {
-  if (ode == ODE_MFMA && !HAS_MFMA) ode = ODE_VALU;
-  switch (ode * 2 + (drop ? 1 : 0)) {
-    case ODE_MFMA * 2 + 0: return seg_forward_t<false, ODE_MFMA>(a, tails, st);
-    case ODE_MFMA * 2 + 1: return seg_forward_t<true, ODE_MFMA>(a, tails, st);
-    case ODE_VALU_LDS * 2 + 0: return seg_forward_t<false, ODE_VALU_LDS>(a, tails, st);
-    case ODE_VALU_LDS * 2 + 1: return seg_forward_t<true, ODE_VALU_LDS>(a, tails, st);
-    case ODE_VALU * 2 + 1: return seg_forward_t<true, ODE_VALU>(a, tails, st);
-    default: return seg_forward_t<false, ODE_VALU>(a, tails, st);
-  }
+hipError_t NJ_CAT(njode_seg_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  return with_drop(r.drop, [&](auto D) {
+    constexpr bool DROP = decltype(D)::value;
+    switch (r.seg_ode) {
+      case ODE_MFMA: return seg_forward_t<DROP, ODE_MFMA>(a, r, st);
+      case ODE_VALU_LDS: return seg_forward_t<DROP, ODE_VALU_LDS>(a, r, st);
+      default: return seg_forward_t<DROP, ODE_VALU>(a, r, st);
+    }
+  });
 }
 
 const CfgOps* NJ_CAT(njode_cfg_ops_, NJ_ID)() {
@@ -371,6 +360,7 @@ const CfgOps* NJ_CAT(njode_cfg_ops_, NJ_ID)() {
       FRAG2_OFF,
       ACT_FLOATS,
       HAS_Q4 ? Q4_ACT_FLOATS : 0,
+      HAS_MFMA_LOCK ? 1 : 0,
       HAS_MFMA_SWEEP ? 1 : 0,
       HAS_CHAIN ? 1 : 0,
       HAS_SEG_CHAIN ? 1 : 0,
@@ -381,11 +371,11 @@ const CfgOps* NJ_CAT(njode_cfg_ops_, NJ_ID)() {
 #endif
 
 #if NJ_PART == 1
-template <bool DROP, int ODE> static hipError_t seg_backward_t(const KArgs& a, hipStream_t st) {
+template <bool DROP, int ODE> static hipError_t seg_backward_t(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (C::MASKED || C::RNN) {
     return hipErrorNotSupported;
   } else if constexpr (ODE == ODE_MFMA) {
-    launch_mfma_rows_bwd<C, DROP>(a, a.ode_split != 0, st);
+    launch_mfma_rows_bwd<C, DROP>(a, r, st);
     return hipGetLastError();
   } else {
     {
@@ -404,44 +394,27 @@ template <bool DROP, int ODE> static hipError_t seg_backward_t(const KArgs& a, h
     return hipGetLastError();
   }
 }
-hipError_t NJ_CAT(njode_seg_backward_, NJ_ID)(const KArgs& a, bool drop, int ode, hipStream_t st) {
-  if (ode == ODE_MFMA && !HAS_MFMA) ode = ODE_VALU;
-  switch (ode * 2 + (drop ? 1 : 0)) {
-    case ODE_MFMA * 2 + 0: return seg_backward_t<false, ODE_MFMA>(a, st);
-    case ODE_MFMA * 2 + 1: return seg_backward_t<true, ODE_MFMA>(a, st);
-    case ODE_VALU_LDS * 2 + 0: return seg_backward_t<false, ODE_VALU_LDS>(a, st);
-    case ODE_VALU_LDS * 2 + 1: return seg_backward_t<true, ODE_VALU_LDS>(a, st);
-    case ODE_VALU * 2 + 1: return seg_backward_t<true, ODE_VALU>(a, st);
-    default: return seg_backward_t<false, ODE_VALU>(a, st);
-  }
+hipError_t NJ_CAT(njode_seg_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  return with_drop(r.drop, [&](auto D) {
+    constexpr bool DROP = decltype(D)::value;
+    switch (r.seg_ode) {
+      case ODE_MFMA: return seg_backward_t<DROP, ODE_MFMA>(a, r, st);
+      case ODE_VALU_LDS: return seg_backward_t<DROP, ODE_VALU_LDS>(a, r, st);
+      default: return seg_backward_t<DROP, ODE_VALU>(a, r, st);
+    }
+  });
 }
 #endif
 
 #if NJ_PART == 2
-template <class CC> static void lock_pack_frags(const KArgs& a, hipStream_t st) {
-  if constexpr (HAS_MFMA_LOCK) {
-    using ES = typename EncS<CC>::type;
-    using DS = typename DecS<CC>::type;
-    k_pack_frags<CC><<<cdiv(MF<CC>::NALL * 64, 256), 256, 0, st>>>(a.P, a.frag);
-    k_pack_net<typename CC::Enc, ES><<<cdiv(ES::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_ENC,
-                                                                             a.frag_enc);
-    k_pack_net<typename CC::Dec, DS><<<cdiv(DS::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_DEC,
-                                                                             a.frag_dec);
-  }
-}
-template <class CC, bool DROP> static void lock_launch_mfma(const KArgs& a, hipStream_t st) {
-  if constexpr (HAS_CHAIN) {
-    if (a.chain && !(a.want_path && DROP)) {   // (prediction calls: dropout-free ones)
-      (void)NJ_CAT(njode_chain_forward_, NJ_ID)(a, DROP, st);
-      return;
-    }
-  }
-  if constexpr (HAS_Q4) {
-    if (!a.want_path && lock4_on() && (!a.save_traj || a.lact)) {
+template <class CC, bool DROP> static void lock_launch_mfma(const KArgs& a, const Route& r, hipStream_t st) {
+  if (r.lock_fwd_kind == LOCK_CHAIN) {
+    NJ_CAT(njode_chain_forward_, NJ_ID)(a, r, st);
+  } else if (r.lock_fwd_kind == LOCK_TILE4) {
+    if constexpr (HAS_Q4) {
       const int n_tiles = cdiv(a.B, a.q4_pt);
       KArgs ab = a;
-      static const bool bits_off = getenv("NJODE_DROP_BITS_AHEAD") && atoi(getenv("NJODE_DROP_BITS_AHEAD")) == 0;
-      if (DROP && a.dbits && a.dbits_row && !bits_off) {
+      if (r.lock_bits_ahead) {
         // the keep bits of every evaluation of the forward, drawn ahead in parallel over the chip
         const long long items = (long long)a.K * n_tiles;
         const int nb = (int)(items / 4 + 1 < 2048 ? items / 4 + 1 : 2048);
@@ -449,61 +422,44 @@ template <class CC, bool DROP> static void lock_launch_mfma(const KArgs& a, hipS
         ab.dbits_ready = 1;
       }
       k_paths_fwd_q4<CC, DROP><<<n_tiles, 256, 0, st>>>(ab);
-      return;
     }
-  }
-  if constexpr (HAS_MFMA_LOCK) k_paths_fwd_mfma<CC, DROP><<<cdiv(a.B, 32), 128, 0, st>>>(a);
-}
-template <bool DROP> static hipError_t lock_t(KArgs a, bool path, bool loss, int ode, hipStream_t st) {
-  a.want_path = path ? 1 : 0;
-  a.want_loss = loss ? 1 : 0;
-  if (ode == ODE_MFMA && HAS_MFMA_LOCK) {
-    // (the wave-per-path kernels read the flat parameter vector themselves)
-    const bool chain = HAS_CHAIN && a.chain && !(a.want_path && DROP);
-    if (!chain) lock_pack_frags<C>(a, st);
-    ProfScope ps(chain ? "k_paths_fwd_chain" : "k_paths_fwd_mfma", st);
-    lock_launch_mfma<C, DROP>(a, st);
   } else {
-    ProfScope ps("k_paths_fwd", st);
-    k_paths_fwd<C, DROP><<<cdiv(a.B, 64), 64, 0, st>>>(a);
+    if constexpr (HAS_MFMA_LOCK) k_paths_fwd_mfma<CC, DROP><<<cdiv(a.B, 32), 128, 0, st>>>(a);
   }
+}
+template <bool DROP> static hipError_t lock_t(KArgs a, const Route& r, hipStream_t st) {
+  a.want_path = r.want_path ? 1 : 0;
+  a.want_loss = r.want_loss ? 1 : 0;
+  // (the wave-per-path kernels read the flat parameter vector themselves)
+  if (r.lock_fwd_kind == LOCK_WAVE1 || r.lock_fwd_kind == LOCK_TILE4) lock_pack_frags<C>(a, st);
+  ProfScope ps(lock_name(r.lock_fwd_kind, false), st);
+  if (r.lock_fwd_kind == LOCK_VALU) k_paths_fwd<C, DROP><<<cdiv(a.B, 64), 64, 0, st>>>(a);
+  else lock_launch_mfma<C, DROP>(a, r, st);
   return hipGetLastError();
 }
-hipError_t NJ_CAT(njode_lock_forward_, NJ_ID)(const KArgs& a, bool drop, bool path, bool loss, int ode,
-                                             hipStream_t st) {
-  return drop ? lock_t<true>(a, path, loss, ode, st) : lock_t<false>(a, path, loss, ode, st);
+hipError_t NJ_CAT(njode_lock_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  return with_drop(r.drop, [&](auto D) { return lock_t<decltype(D)::value>(a, r, st); });
 }
 #endif
 
 #if NJ_PART == 3
-template <class CC, bool DROP> static void lock_bwd_mfma(const KArgs& a, hipStream_t st) {
+template <class CC, bool DROP> static void lock_bwd_mfma(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_MFMA_SWEEP) {
-    using ES = typename EncS<CC>::type;
-    using DS = typename DecS<CC>::type;
-    k_pack_frags<CC><<<cdiv(MF<CC>::NALL * 64, 256), 256, 0, st>>>(a.P, a.frag);
-    k_pack_net<typename CC::Enc, ES><<<cdiv(ES::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_ENC,
-                                                                             a.frag_enc);
-    k_pack_net<typename CC::Dec, DS><<<cdiv(DS::NALL * 64, 256), 256, 0, st>>>(a.P + CC::OFF_DEC,
-                                                                             a.frag_dec);
+    lock_pack_frags<CC>(a, st);
     {
-      const bool chain = HAS_CHAIN && a.chain;
-      ProfScope ps(chain ? "k_paths_bwd_adj_chain" : "k_paths_bwd_adj_mfma", st);
-      bool q4 = false;
-      if constexpr (HAS_CHAIN) {
-        if (chain) {
-          (void)NJ_CAT(njode_chain_sweep_, NJ_ID)(a, DROP, st);
-          q4 = true;
-        }
+      // (the family whose records the saving forward wrote: Route::lock_bwd_kind)
+      ProfScope ps(lock_name(r.lock_bwd_kind, true), st);
+      if (r.lock_bwd_kind == LOCK_CHAIN) {
+        NJ_CAT(njode_chain_sweep_, NJ_ID)(a, r, st);
+      } else if (r.lock_bwd_kind == LOCK_TILE4) {
+        if constexpr (HAS_Q4) k_paths_bwd_adj_q4<CC, DROP><<<cdiv(a.B, a.q4_pt), 256, 0, st>>>(a);
+      } else {
+        k_paths_bwd_adj_mfma<CC, DROP><<<cdiv(a.B, 16), 64, 0, st>>>(a);
       }
-      if constexpr (HAS_Q4) {
-        if (!q4 && lock4_on() && a.lact) {   // (lact: the saving forward was k_paths_fwd_q4)
-          k_paths_bwd_adj_q4<CC, DROP><<<cdiv(a.B, a.q4_pt), 256, 0, st>>>(a);
-          q4 = true;
-        }
-      }
-      if (!q4) k_paths_bwd_adj_mfma<CC, DROP><<<cdiv(a.B, 16), 64, 0, st>>>(a);
     }
-    if (!NJ_CAT(njode_chain_dw_, NJ_ID)(a, st)) {
+    if (r.dw_stored) {
+      NJ_CAT(njode_chain_dw_, NJ_ID)(a, st);
+    } else {
       ProfScope ps("k_ode_dw_pairs_mfma", st);
       k_ode_dw_pairs_mfma<CC, DROP><<<a.n_waves_rows / 4, 256, 0, st>>>(a);
     }
@@ -525,7 +481,7 @@ template <class CC, bool DROP> static hipError_t lock_bwd_valu(const KArgs& a, h
     return hipErrorNotSupported;
   } else {
     {
-      ProfScope ps("k_paths_bwd_adj", st);
+      ProfScope ps(lock_name(LOCK_VALU, true), st);
       k_paths_bwd_adj<CC, DROP><<<cdiv(a.B, 64), 64, 0, st>>>(a);
     }
     {
@@ -547,125 +503,105 @@ template <class CC, bool DROP> static hipError_t lock_bwd_valu(const KArgs& a, h
     return hipGetLastError();
   }
 }
-template <bool DROP> static hipError_t lock_bwd_t(const KArgs& a, int ode, hipStream_t st) {
-  if (ode == ODE_MFMA && HAS_MFMA_SWEEP) {
-    lock_bwd_mfma<C, DROP>(a, st);
-    return hipGetLastError();
-  }
-  return lock_bwd_valu<C, DROP>(a, st);
+template <bool DROP> static hipError_t lock_bwd_t(const KArgs& a, const Route& r, hipStream_t st) {
+  if (r.lock_bwd_kind == LOCK_VALU) return lock_bwd_valu<C, DROP>(a, st);
+  lock_bwd_mfma<C, DROP>(a, r, st);
+  return hipGetLastError();
 }
-hipError_t NJ_CAT(njode_lock_backward_, NJ_ID)(const KArgs& a, bool drop, int ode, hipStream_t st) {
-  return drop ? lock_bwd_t<true>(a, ode, st) : lock_bwd_t<false>(a, ode, st);
+hipError_t NJ_CAT(njode_lock_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  return with_drop(r.drop, [&](auto D) { return lock_bwd_t<decltype(D)::value>(a, r, st); });
 }
 #endif
 
-#if NJ_PART >= 4
-// waves (= paths) per block: as few as still give every path a SIMD of its own
-static inline int chain_waves_per_block(int B) {
-  static const int env = getenv("NJODE_CHAIN_WPB") ? atoi(getenv("NJODE_CHAIN_WPB")) : 0;
-  if (env >= 1 && env <= CHAIN_MAX_WAVES) return env;
-  int w = 1;
-  while (w < CHAIN_MAX_WAVES && cdiv(B, w) > 256) w *= 2;
-  return w;
-}
-#endif
+// Parts 4 and 5, the wave-per-chain kernels.  Their launches too live in templates on the configuration
+// (`if constexpr` then discards them for the other shapes); the functions the other parts call wrap them.
 #if NJ_PART == 4
-hipError_t NJ_CAT(njode_chain_forward_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st) {
+template <class CC> static void chain_forward(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_CHAIN) {
-    const int wpb = chain_waves_per_block(a.B);
-    if (drop) {
+    const int wpb = r.chain_wpb;
+    if (r.drop) {
       const long long items = (long long)a.K * a.B + (long long)a.n_obs * 3 + a.B;
       const int nb = (int)(items / 256 + 1 < 4096 ? items / 256 + 1 : 4096);
-      k_chain_bits<C><<<nb, 256, 0, st>>>(a);
-      k_paths_fwd_chain<C, true><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
-    } else {
-      k_paths_fwd_chain<C, false><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
+      k_chain_bits<CC><<<nb, 256, 0, st>>>(a);
     }
-    return hipGetLastError();
-  } else {
-    return hipErrorNotSupported;
+    with_drop(r.drop, [&](auto D) {
+      k_paths_fwd_chain<CC, decltype(D)::value><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
+    });
   }
 }
-#endif
-
-#if NJ_PART == 4
-hipError_t NJ_CAT(njode_seg_chain_forward_, NJ_ID)(const KArgs& a, bool drop, bool tails, hipStream_t st) {
+template <class CC> static void seg_chain_forward(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_SEG_CHAIN) {
-    const int nb = cdiv(a.n_obs + a.B, 4);
-    if (drop && !a.dbits_ready) {
+    const int nb = cdiv(a.n_obs + a.B, 4), tails = r.tails_ride ? 1 : 0;
+    if (r.drop && !a.dbits_ready) {
       const long long items = (long long)a.K * a.B;
-      k_seg_chain_bits<C><<<(int)(items / 256 + 1 < 2048 ? items / 256 + 1 : 2048), 256, 0, st>>>(a);
+      k_seg_chain_bits<CC><<<(int)(items / 256 + 1 < 2048 ? items / 256 + 1 : 2048), 256, 0, st>>>(a);
     }
-    if (a.plan_job) {
-      // the next batch's plan rides in front of this launch's own blocks (njode_plan.h)
-      const PlanJob job = *(const PlanJob*)a.plan_job;
-      if (drop) k_seg_fwd_chain_plan<C, true><<<nb + job.P, 256, 0, st>>>(a, tails ? 1 : 0, job);
-      else k_seg_fwd_chain_plan<C, false><<<nb + job.P, 256, 0, st>>>(a, tails ? 1 : 0, job);
-    } else {
-      if (drop) k_seg_fwd_chain<C, true><<<nb, 256, 0, st>>>(a, tails ? 1 : 0);
-      else k_seg_fwd_chain<C, false><<<nb, 256, 0, st>>>(a, tails ? 1 : 0);
-    }
-    return hipGetLastError();
-  } else {
-    return hipErrorNotSupported;
+    with_drop(r.drop, [&](auto D) {
+      if (a.plan_job) {
+        // the next batch's plan rides in front of this launch's own blocks (njode_plan.h)
+        const PlanJob job = *(const PlanJob*)a.plan_job;
+        k_seg_fwd_chain_plan<CC, decltype(D)::value><<<nb + job.P, 256, 0, st>>>(a, tails, job);
+      } else {
+        k_seg_fwd_chain<CC, decltype(D)::value><<<nb, 256, 0, st>>>(a, tails);
+      }
+    });
   }
+}
+void NJ_CAT(njode_chain_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) { chain_forward<C>(a, r, st); }
+void NJ_CAT(njode_seg_chain_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  seg_chain_forward<C>(a, r, st);
 }
 #endif
 
 #if NJ_PART == 5
-hipError_t NJ_CAT(njode_seg_chain_backward_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st) {
+template <class CC> static void chain_dw(const KArgs& a, hipStream_t st) {
+  if constexpr ((HAS_CHAIN || HAS_SEG_CHAIN) && C::W < 64) {
+    ProfScope ps("k_ode_dw_stored", st);
+    k_ode_dw_stored<CC><<<a.dw_pair_blocks + a.dw_seg_blocks, 256, 0, st>>>(a, a.dw_pair_blocks);
+  }
+}
+template <class CC> static void chain_dw_enc(const KArgs& a, const Route& r, hipStream_t st) {
+  if constexpr (HAS_SEG_CHAIN && C::W < 64) {
+    ProfScope ps("k_ode_dw_stored_enc", st);
+    const int nb = a.dw_pair_blocks + a.dw_seg_blocks + a.n_waves_rows / 4;
+    with_drop(r.drop, [&](auto D) {
+      k_ode_dw_stored_enc<CC, decltype(D)::value><<<nb, 256, 0, st>>>(a, a.dw_pair_blocks, a.dw_seg_blocks);
+    });
+  }
+}
+template <class CC> static void seg_chain_backward(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_SEG_CHAIN) {
     {
       ProfScope ps("k_seg_bwd_chain", st);
-      if (drop) k_seg_bwd_chain<C, true><<<cdiv(a.n_obs, 4), 256, 0, st>>>(a);
-      else k_seg_bwd_chain<C, false><<<cdiv(a.n_obs, 4), 256, 0, st>>>(a);
+      with_drop(r.drop, [&](auto D) { k_seg_bwd_chain<CC, decltype(D)::value><<<cdiv(a.n_obs, 4), 256, 0, st>>>(a); });
     }
     // d loss / d ODE parameters: from the sweep's records (with the encoder's pass in the same launch),
     // else the lockstep plan's pair kernel on the stored adjoints
-    if (a.dw_enc_fused) {
-      if (!NJ_CAT(njode_chain_dw_enc_, NJ_ID)(a, drop, st)) return hipErrorLaunchFailure;
-    } else if (!NJ_CAT(njode_chain_dw_, NJ_ID)(a, st)) {
+    if (r.dw_enc_fused) {
+      chain_dw_enc<CC>(a, r, st);
+    } else if (r.dw_stored) {
+      chain_dw<CC>(a, st);
+    } else {
       ProfScope ps("k_ode_dw_pairs_mfma", st);
-      if (drop) k_ode_dw_pairs_mfma<C, true><<<a.n_waves_rows / 4, 256, 0, st>>>(a);
-      else k_ode_dw_pairs_mfma<C, false><<<a.n_waves_rows / 4, 256, 0, st>>>(a);
+      with_drop(r.drop, [&](auto D) {
+        k_ode_dw_pairs_mfma<CC, decltype(D)::value><<<a.n_waves_rows / 4, 256, 0, st>>>(a);
+      });
     }
-    return hipGetLastError();
-  } else {
-    return hipErrorNotSupported;
   }
 }
-bool NJ_CAT(njode_chain_dw_, NJ_ID)(const KArgs& a, hipStream_t st) {
-  if constexpr ((HAS_CHAIN || HAS_SEG_CHAIN) && C::W < 64) {
-    if (!(a.chain || a.seg_chain) || !a.cdelta || !a.cseg || a.dw_pair_blocks <= 0) return false;
-    ProfScope ps("k_ode_dw_stored", st);
-    k_ode_dw_stored<C><<<a.dw_pair_blocks + a.dw_seg_blocks, 256, 0, st>>>(a, a.dw_pair_blocks);
-    return true;
-  } else {
-    return false;
-  }
-}
-bool NJ_CAT(njode_chain_dw_enc_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st) {
-  if constexpr (HAS_SEG_CHAIN && C::W < 64) {
-    if (!a.seg_chain || !a.cdelta || !a.cseg || a.dw_pair_blocks <= 0) return false;
-    ProfScope ps("k_ode_dw_stored_enc", st);
-    const int nb = a.dw_pair_blocks + a.dw_seg_blocks + a.n_waves_rows / 4;
-    if (drop) k_ode_dw_stored_enc<C, true><<<nb, 256, 0, st>>>(a, a.dw_pair_blocks, a.dw_seg_blocks);
-    else k_ode_dw_stored_enc<C, false><<<nb, 256, 0, st>>>(a, a.dw_pair_blocks, a.dw_seg_blocks);
-    return true;
-  } else {
-    return false;
-  }
-}
-hipError_t NJ_CAT(njode_chain_sweep_, NJ_ID)(const KArgs& a, bool drop, hipStream_t st) {
+template <class CC> static void chain_sweep(const KArgs& a, const Route& r, hipStream_t st) {
   if constexpr (HAS_CHAIN) {
-    const int wpb = chain_waves_per_block(a.B);
-    if (drop) k_paths_bwd_adj_chain<C, true><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
-    else k_paths_bwd_adj_chain<C, false><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
-    return hipGetLastError();
-  } else {
-    return hipErrorNotSupported;
+    const int wpb = r.chain_wpb;
+    with_drop(r.drop, [&](auto D) {
+      k_paths_bwd_adj_chain<CC, decltype(D)::value><<<cdiv(a.B, wpb), 64 * wpb, 0, st>>>(a);
+    });
   }
 }
+void NJ_CAT(njode_seg_chain_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
+  seg_chain_backward<C>(a, r, st);
+}
+void NJ_CAT(njode_chain_dw_, NJ_ID)(const KArgs& a, hipStream_t st) { chain_dw<C>(a, st); }
+void NJ_CAT(njode_chain_sweep_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) { chain_sweep<C>(a, r, st); }
 #endif
 
 }  // namespace njode

@@ -17,27 +17,26 @@ constexpr int ODE_MFMA = 0, ODE_VALU = 1, ODE_VALU_LDS = 2;
 // (NJODE_ODE=mfma1 keeps ODE_MFMA but with one wave per tile, njode_mfma.h, where the default
 // picks the mixed kernels of njode_mfma_split.h: A/B baseline)
 
+struct Route;   // njode_route.h: what a call runs, decided once; the launchers switch on it
+
 struct CfgOps {
   NjodeDims dims;
   int P;          // flat parameter count
   int ode_in, enc_in;
   int off_enc, off_dec;  // start of the encoder / readout slices in the flat vector
   // segment plan
-  // tails: also evolve every path from its last observation to the end of the schedule
-  // (hT); ode: implementation of the ODE-evolve kernels (ODE_*)
-  hipError_t (*seg_forward)(const KArgs&, bool drop, bool tails, int ode, hipStream_t);
-  hipError_t (*seg_backward)(const KArgs&, bool drop, int ode, hipStream_t);
+  hipError_t (*seg_forward)(const KArgs&, const Route&, hipStream_t);
+  hipError_t (*seg_backward)(const KArgs&, const Route&, hipStream_t);
   // lockstep plan
-  // ode: ODE_MFMA runs the matrix-core lockstep kernel where the shape has one
-  hipError_t (*lock_forward)(const KArgs&, bool drop, bool path, bool loss, int ode, hipStream_t);
-  // ode: the implementation the saving forward ran (decides the dropout keying)
-  hipError_t (*lock_backward)(const KArgs&, bool drop, int ode, hipStream_t);
+  hipError_t (*lock_forward)(const KArgs&, const Route&, hipStream_t);
+  hipError_t (*lock_backward)(const KArgs&, const Route&, hipStream_t);
   int frag_floats;  // size of the fragment buffer (0: no MFMA kernels for this shape)
   int frag_enc_off, frag_dec_off;  // offsets of the encoder / readout fragments in it
   int frag2_off;                   // ... of the scaled ODE table (njode_ode2.h)
   int act_floats;                  // stored ODE activations per chain and Euler step (0: none)
   int lock_act_floats;             // lockstep plan (masked shapes): ... per tile of 16 paths and step
-  int lock_sweep_mfma;  // the lockstep backward has a matrix-core adjoint sweep
+  int lock_fwd_mfma;    // the lockstep forward has matrix-core kernels
+  int lock_sweep_mfma;  // ... and the lockstep backward a matrix-core adjoint sweep
   int lock_chain;       // ... and the lockstep plan has the wave-per-path kernels (njode_chain.h)
   int seg_chain;        // the segment plan has the wave-per-item ODE kernels (njode_chain_seg.h)
   int ode_split;        // ODE_MFMA runs the mixed ODE kernels (njode_mfma_split.h)

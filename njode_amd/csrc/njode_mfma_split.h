@@ -805,14 +805,6 @@ __global__ void __launch_bounds__(256, 2) k_ode_fwd_split(KArgs a) {
   ode_fwd_split<C, DROP, TAIL, false>(a, (lfp)lds_raw, blockIdx.x, gridDim.x, 0, (n_items + 15) / 16);
 }
 
-// Tails of a LARGE plan (round 5): one wave per tile on the scaled fragments, like the bulk of
-// the mixed kernel -- the tails run BESIDE the items' forward on a busy chip, where the throughput
-// per SIMD counts, not the latency of one tile (the four-wave form above: ~20 % less per SIMD)
-template <class C, bool DROP>
-__global__ void __launch_bounds__(64) k_ode_fwd_tails(KArgs a) {
-  ode2_fwd_single<C, DROP, true, false>(a, threadIdx.x, blockIdx.x, gridDim.x, 0, (a.B + 15) / 16);
-}
-
 // Mixed form.  Tiles are sorted by length; the split point T (k_split_point, on the device)
 // hands the T longest tiles to the first `ns` blocks, which run them with four waves per tile
 // (low latency per Euler step), and the rest to the other blocks, whose waves each run a tile

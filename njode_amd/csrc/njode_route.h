@@ -1,7 +1,8 @@
 // njode_route.h -- which kernel family a call of the compiled shapes runs on, decided ONCE: the NJODE_*
 // switches (Env), what the workspace is sized for (Sizing) and what is launched (Route).  Host only; included
-// by njode_api.hip, which sizes (make_layout), plans (build_plan) and launches (njode_forward_f32 /
-// backward_impl) from these fields and derives nothing of its own.
+// by njode_api.hip, which sizes (make_layout), plans (build_plan) and calls the launchers (njode_forward_f32 /
+// backward_impl) from these fields, and by njode_cfg.hip, whose launchers switch on the Route they are
+// handed; neither derives anything of its own.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -11,14 +12,15 @@
 
 namespace njode {
 
-// ---- the switches: every NJODE_* variable njode_api.hip reads, parsed once per process by
-// parse_env(), which states each one's values, default and effect (DESIGN.md section 4g mirrors it)
+// ---- the switches: every NJODE_* variable njode_api.hip and njode_cfg.hip act on, parsed once per
+// process by parse_env(), which states each one's values, default and effect (DESIGN.md section 4g
+// mirrors it)
 struct Env {
-  bool generic, ode_one_wave, sort_merge, sort_rocprim, item_pack, chain_delta, lock_sweep_valu, bwd_queue,
+  bool lock4, drop_bits_ahead, generic, ode_one_wave, sort_merge, sort_rocprim, item_pack, chain_delta, lock_sweep_valu, bwd_queue,
       enc_fused, dw_enc_fused, tail_sort_rocprim, validate, plan_sort, plan_grid, plan_stamps, plan_stream,
       plan_grid_tail;
   int lock4_pt, chain_max, seg_chain_max, ode, split_bwd_blocks, split_fwd_blocks, bwd_blocks, fwd_blocks,
-      plan_blocks, cs_shift, plan_inline_max, plan_inline_blocks;
+      plan_blocks, cs_shift, plan_inline_max, plan_inline_blocks, enc_blocks, chain_wpb;
   float split_r_bwd, split_r_fwd;
   double rec_budget_gb;
 };
@@ -29,8 +31,12 @@ inline Env parse_env() {
   const auto on = [](const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; };         // default off
   const auto not_off = [](const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); };  // default on
   const auto is = [](const char* e, const char* v) { return e && strcmp(e, v) == 0; };
-  const char *ode = getenv("NJODE_ODE"), *sort = getenv("NJODE_SORT");
+  const char *ode = getenv("NJODE_ODE"), *sort = getenv("NJODE_SORT"), *lock4 = getenv("NJODE_LOCK4");
   Env e;
+  e.lock4 = !(lock4 && lock4[0] == '0');                // =0: masked shapes keep the one-wave lockstep kernels (A/B)
+  e.drop_bits_ahead = not_off("NJODE_DROP_BITS_AHEAD"); // =0: the four-wave forwards draw their keep bits themselves (A/B)
+  e.enc_blocks = num("NJODE_ENC_BLOCKS", 4096);         // grid cap of k_encode_rows_mfma (A/B)
+  e.chain_wpb = num("NJODE_CHAIN_WPB", 0);              // =1..8: waves (= paths) per block of the wave-per-path kernels (else: by batch size)
   e.generic = on("NJODE_GENERIC");                      // =1: every model runs the shape-generic kernels (njode_gen.h; A/B, parity tests)
   e.rec_budget_gb = real("NJODE_REC_BUDGET_GB", 16.0);  // bound of the training records, see record_budget_bytes()
   e.lock4_pt = num("NJODE_LOCK4_PT", 0);                // =1|2|4|8|16: paths per tile of the masked lockstep kernels (else: by batch size)
@@ -134,6 +140,7 @@ struct Sizing {
   bool seg_act;           // the segment plan's forward stores its hidden activations (KArgs::act)
   bool pack;              // ... and the items packed for the backward (KArgs::item_pack, tile_last)
   bool lock_act;          // the lockstep forward stores its activations (KArgs::lact, jact)
+  bool lock_bits;         // ... and has buffers for keep bits drawn ahead of it (KArgs::dbits, dbits_row)
   bool delta, delta_seg;  // the wave-per-chain sweeps store delta1 | delta2 (KArgs::cdelta), and their segment sums (cseg)
   int n_waves;            // one wave per tile of 16 rows until the chip is full (+ the split blocks' slab rows)
   int n_waves_lock;       // waves (= slab rows) of the lockstep plan's matrix-core dW kernels
@@ -173,6 +180,7 @@ inline Sizing size_call(const CfgOps& o, int B, int n_obs, int n_times, int K, i
   z.seg_act = z.save && o.act_floats > 0 && z.seg_untailed && n_obs > 0;
   z.pack = z.seg_act && e.item_pack;
   z.lock_act = z.save && (z.chain || (o.lock_act_floats > 0 && !want_path));
+  z.lock_bits = z.train && (z.chain || z.lock_act);
   // ... where they fit the record budget beside the activations (else the pair dW kernel recomputes them)
   z.delta = z.save && e.chain_delta && (z.chain || (z.seg_act && z.seg_items)) &&
             (double)B * steps * (2.0 * CHAIN_ACT_FLOATS * 4.0 + 16.0) <= rec_budget;
@@ -192,11 +200,15 @@ inline Sizing size_call(const CfgOps& o, int B, int n_obs, int n_times, int K, i
 // these fields into KArgs; build_plan, the forward and the backward read them. The sizing part may
 // OVER-provision relative to dispatch (it admits seg_items for a call whose schedule then has a tail, or whose
 // NJODE_ODE leaves the split kernels, and sizes `act` for the wave-per-item records all the same); it must
-// never under-provision: prepare() checks that seg_chain implies size.seg_items (and KArgs::chain size.chain)
-// before anything is launched.
+// never under-provision: prepare() checks route_admitted() before anything is launched.
+// Kernel family of the lockstep plan's forward / adjoint sweep: VALU, one wave per tile of 16 or 32 paths
+// (njode_mfma_lockstep.h), one tile over the four waves of a block (njode_mfma_lock4.h; NJODE_LOCK4=0
+// keeps the one-wave kernels), one wave per path (njode_chain.h)
+enum LockKind { LOCK_VALU, LOCK_WAVE1, LOCK_TILE4, LOCK_CHAIN };
 struct Route {
   Sizing size;
   bool drop;            // dropout masks are drawn
+  bool want_path, want_loss;   // NJODE_C_RETURN_PATH, NJODE_C_GET_LOSS (the lockstep forward's outputs)
   bool seg;             // segment plan (else lockstep): unmasked, loss requested, no path output, schedule ends at its last jump
   bool tails;           // ... which also evolves every path from its last observation to the end (hT)
   int ode;              // implementation of the ODE-evolve kernels (ODE_*)
@@ -205,19 +217,41 @@ struct Route {
   // regenerates the dropout masks, so a forward that saves for it must key them as the sweep
   // does: the matrix-core keying where the shape has a matrix-core sweep, the VALU keying otherwise.
   int lock_sweep, lock_fwd;
+  // ... and the kernel family of each.  The sweep reads the records of the family that saved them (lact /
+  // jact of the four-wave tiles or of the wave-per-path kernels): both kinds come from lock_kind() on the
+  // call's sizing and flags, so the two calls of a step agree.
+  int lock_fwd_kind, lock_bwd_kind;
+  bool lock_bits_ahead; // the four-wave tiles' forward reads keep bits drawn ahead of it (k_q4_bits)
+  int chain_wpb;        // waves (= paths) per block of the wave-per-path kernels
   bool lock_mfma;       // the lockstep backward runs on the matrix cores
+  int seg_ode;          // ODE-evolve implementation of the segment plan: `ode` where the shape has it
   int ode_split;        // the mixed ODE kernels (njode_mfma_split.h)
   int seg_chain;        // the wave-per-item ODE kernels (njode_chain_seg.h)
   int enc_fused;        // the ODE forward's one-wave role evaluates the encoder
+  int enc_blocks;       // grid cap of k_encode_rows_mfma
+  bool tails_ride;      // the tails ride in the items' launch (k_seg_fwd_chain), else in one of their own
+  // keep bits of the segment plan's ODE forward are drawn ahead, by spare blocks of the fragment-pack launch
+  bool seg_bits_ahead;
+  bool side, tails_side;   // the call has helper streams (route_side), and the tails run on the second one
   int defer_loss;       // 1: the loss is summed by the backward call (fused step), 2: rows in the forward call
   int dw_enc_fused;     // the encoder's weight-gradient pass rides in k_ode_dw_stored's launch
   int tile_q_on;        // the mixed ODE backward pops its tiles from a queue
   int n_split_blocks, n_blocks_bwd, n_split_fwd, n_blocks_fwd;   // four-wave / all blocks of the mixed kernels
   int dw_pair_blocks, dw_seg_blocks;   // k_ode_dw_stored's roles
   bool chain_dw;        // the wave-per-chain sweeps' own weight-gradient kernel runs (njode_chain_dw.h)
+  bool dw_stored;       // ... as k_ode_dw_stored, a launch of its own (no (step, path) pairs at K = 0: the pair kernel)
   bool hosts_plan;      // this forward's ODE launch can carry a deferred plan in front of its blocks
   bool needs_PT;        // the backward reads the transposed parameter copy (VALU kernels only)
 };
+
+// (z.chain already excludes prediction calls that draw dropout masks; the four-wave tiles neither
+// return paths nor save without their records)
+inline int lock_kind(const CfgOps& o, const Sizing& z, const Env& e, bool mfma, bool want_path) {
+  if (!mfma) return LOCK_VALU;
+  if (z.chain) return LOCK_CHAIN;
+  if (o.lock_act_floats > 0 && !want_path && e.lock4 && (!z.save || z.lock_act)) return LOCK_TILE4;
+  return LOCK_WAVE1;
+}
 
 // cus: compute units of the device (read only with NJODE_BWD_QUEUE=1)
 inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int K, int call_flags,
@@ -225,6 +259,8 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
   Route r;
   r.size = z;
   r.drop = drop;
+  r.want_path = (call_flags & NJODE_C_RETURN_PATH) != 0;
+  r.want_loss = (call_flags & NJODE_C_GET_LOSS) != 0;
   r.seg = z.seg_any && n_obs > 0 && !tail && !(call_flags & NJODE_C_GEN_LOCKSTEP);
   r.tails = r.seg && want_hT;
   r.ode = e.ode;
@@ -238,7 +274,15 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
   // ... and a forward that saves for a sweep which reads its stored activations (masked shapes,
   // njode_mfma_lock4.h) has to be the implementation that stores them
   r.lock_fwd = (z.lock_act || drop) ? r.lock_sweep : r.ode;
+  r.lock_fwd_kind = lock_kind(o, z, e, r.lock_fwd == ODE_MFMA && o.lock_fwd_mfma, r.want_path);
+  r.lock_bwd_kind = lock_kind(o, z, e, r.lock_sweep == ODE_MFMA, r.want_path);
+  r.lock_bits_ahead = r.lock_fwd_kind == LOCK_TILE4 && drop && z.lock_bits && e.drop_bits_ahead;
+  // as few waves per block as still give every path a SIMD of its own
+  r.chain_wpb = 1;
+  if (e.chain_wpb >= 1 && e.chain_wpb <= CHAIN_MAX_WAVES) r.chain_wpb = e.chain_wpb;
+  else while (r.chain_wpb < CHAIN_MAX_WAVES && cdiv(B, r.chain_wpb) > 256) r.chain_wpb *= 2;
   r.lock_mfma = !r.seg && r.lock_sweep == ODE_MFMA;
+  r.seg_ode = (r.ode == ODE_MFMA && !o.seg_mfma) ? ODE_VALU : r.ode;
   r.ode_split = (r.ode == ODE_MFMA && o.ode_split && !e.ode_one_wave && K <= SPLIT_KMAX) ? 1 : 0;
   // fused step: the matrix-core row kernel of the backward evaluates every readout anyway
   // ... or in the forward call, which then skips its forward-only row pass (NJODE_C_ROWS_IN_FWD)
@@ -269,6 +313,15 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
   // (the wave-per-item forward reads every row's encoder output: k_encode_rows_mfma)
   r.enc_fused = (e.enc_fused && r.seg && r.ode == ODE_MFMA && r.ode_split && r.n_split_fwd < r.n_blocks_fwd &&
                  !r.seg_chain) ? 1 : 0;
+  r.enc_blocks = e.enc_blocks;
+  r.tails_ride = r.tails && r.seg_chain;
+  // (plans whose every tile runs four waves wide, i.e. small batches: there the forward IS the chain of its
+  // longest tile; in the mixed kernel of a large plan the four-wave blocks are ~10 % of the work and the
+  // extra blocks of the pack launch cost more than they save: 20 000 paths, k_pack_all 7.5 -> 12.3 us for
+  // ~1.5 us off k_ode_fwd_mixed) ... and the wave-per-item forward's lane masks
+  r.seg_bits_ahead = r.seg_mfma && drop && z.seg_bits &&
+                     (r.seg_chain || (r.ode_split && e.drop_bits_ahead && r.n_split_fwd == r.n_blocks_fwd));
+  r.side = r.tails_side = false;
   {
     // k_ode_dw_stored: a wave per tile of 16 (step, path) pairs until every SIMD has one (one block per
     // CU: a wave holds all accumulator tiles and the next tile's operands), a few blocks for the segments
@@ -278,10 +331,31 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
     r.dw_seg_blocks = (int)std::min<long long>(std::max<long long>((seg_tiles + 3) / 4, 1), 64);
   }
   r.chain_dw = (z.chain || r.seg_chain) && z.delta && z.delta_seg;
-  r.dw_enc_fused = (e.dw_enc_fused && r.seg_chain && r.chain_dw && r.dw_pair_blocks > 0) ? 1 : 0;
+  r.dw_stored = r.chain_dw && r.dw_pair_blocks > 0;
+  r.dw_enc_fused = (e.dw_enc_fused && r.seg_chain && r.dw_stored) ? 1 : 0;
   r.hosts_plan = r.seg_mfma && r.ode_split && !r.enc_fused;
   r.needs_PT = !(r.lock_mfma || r.seg_mfma);
   return r;
+}
+
+// The one input known only after the plan is built: whether the call has helper streams (build_plan).
+// The tile kernels' keep bits need the complete plan on the pack launch's stream -- the wave-per-item
+// forward's lane masks need nothing of it -- and the tails, unless they ride, take the second stream.
+inline void route_side(Route& r, bool side) {
+  r.side = side;
+  r.tails_side = r.tails && side && !r.tails_ride;
+  r.seg_bits_ahead = r.seg_bits_ahead && (r.seg_chain || !side);
+}
+
+// A kernel must never run on records sized for another: what the dispatch part chose against what the
+// sizing part provided.
+inline bool route_admitted(const Route& r) {
+  const Sizing& z = r.size;
+  const bool chain = r.lock_fwd_kind == LOCK_CHAIN || r.lock_bwd_kind == LOCK_CHAIN;
+  const bool tile4 = r.lock_fwd_kind == LOCK_TILE4 || r.lock_bwd_kind == LOCK_TILE4;
+  return !(r.seg_chain && !z.seg_items) && !(chain && !z.chain) && !(tile4 && z.save && !z.lock_act) &&
+         !(r.seg_bits_ahead && !z.seg_bits) && !(r.lock_bits_ahead && !z.lock_bits) &&
+         !(r.lock_fwd_kind == LOCK_CHAIN && r.drop && !z.lock_bits);
 }
 
 // Slab rows the backward's kernels wrote, per parameter slice (ODE / encoder / readout): what the

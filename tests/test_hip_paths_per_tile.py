@@ -177,6 +177,34 @@ def test_wave_per_item_ode_kernels_match_the_tiles(tmp_path, B):
     assert rel_l2(a[2 + n_h:2 + n_h + n_p], a[2 + n_h + n_p:]) < 1e-5
 
 
+def test_one_wave_masked_kernels_against_float64(tmp_path):
+    """NJODE_LOCK4=0 (with NJODE_CHAIN_MAX=0: no wave-per-path kernels either): the masked shape keeps the
+    one-wave lockstep kernels of njode_mfma_lockstep.h, forward and sweep.  Loss, hT and gradients against
+    the float64 oracle with the route matrix's yardstick and floors, on its PhysioNet-shaped batch."""
+    import test_hip_route_matrix as R
+    job = {'id': 'lock4_off', 'cfg': list(R.PHYSIO), 'batch': 'physio', 'dropout': 0.0}
+    res, info = R.run_child(tmp_path, 'lock4_off', {'NJODE_LOCK4': '0', 'NJODE_CHAIN_MAX': '0'}, [job])['lock4_off']
+    R.check_names('lock4_off', info['names'], ['k_paths_fwd_mfma', 'k_paths_bwd_adj_mfma'],
+                  ['k_paths_fwd_chain', 'k_paths_bwd_adj_chain'])
+    R.check_vs_oracle('lock4_off', 'one_wave_masked', R.PHYSIO, 'physio', res)
+
+
+def test_encoder_grid_cap_does_not_change_a_bit(tmp_path):
+    """NJODE_ENC_BLOCKS=1: k_encode_rows_mfma as ONE block that walks every tile of rows, against the default
+    grid (a block per tile here).  Rows are encoded independently: loss, hT and both gradients bit for bit
+    (demo shape, 24 paths, 100 steps, 10 % observations, dropout on)."""
+    res = {}
+    for tag, env_extra in (('default', {}), ('one_block', {'NJODE_ENC_BLOCKS': '1'})):
+        out = str(tmp_path / (tag + '_enc.npy'))
+        p = subprocess.run([sys.executable, '-c', _SNIPPET_SEG.format(tests=TESTS, repo=REPO, out=out, B=24)],
+                           env=dict(os.environ, **env_extra), cwd=REPO, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-3000:]
+        res[tag] = np.load(out)
+    assert np.isfinite(res['default']).all() and abs(res['default'][0]) > 0
+    assert np.array_equal(res['default'], res['one_block'])
+
+
 def test_weight_gradients_from_stored_operands_match_the_recomputing_kernel(tmp_path):
     """round 6, njode_chain_dw.h: behind the wave-per-chain sweeps the ODE network's weight gradients are
     outer products of operands the sweeps stored (delta1 / delta2 per pair, sums of delta1 per segment for

@@ -67,8 +67,8 @@ def caps(c):
     has_chain = has_q4 and chain_ok
     seg_chain_ok = two and not masked and not rnn and 16 < W <= 64 and H <= 16 and d <= 8
     has_seg_chain = has_split and has_mfma_sweep and seg_chain_ok
-    return dict(HAS_MFMA=has_mfma, HAS_SPLIT=has_split, HAS_Q4=has_q4, HAS_CHAIN=has_chain,
-                HAS_SEG_CHAIN=has_seg_chain)
+    return dict(HAS_MFMA=has_mfma, HAS_SPLIT=has_split, HAS_MFMA_LOCK=has_mfma_lock, HAS_MFMA_SWEEP=has_mfma_sweep,
+                HAS_Q4=has_q4, HAS_CHAIN=has_chain, HAS_SEG_CHAIN=has_seg_chain)
 
 
 ITEMS = ['k_seg_fwd_chain', 'k_seg_bwd_chain']
