@@ -35,8 +35,11 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_collate_count', 'njode_collate_fill',
            'njode_cond_exp_bytes', 'njode_cond_exp_f64',
            'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
+           # include/njode_protocol.h
+           'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
+ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
 SDE_MODELS = {'BlackScholes': 0, 'OrnsteinUhlenbeck': 1, 'Heston': 2}
 # (the fourth model is known to the staged entry points only: njode_generate_stage,
 # njode_cond_exp_staged_f64)
@@ -91,6 +94,13 @@ class NjodeCondExpSchedule(C.Structure):
     _fields_ = [('n_steps', C.c_int32), ('n_times', C.c_int32),
                 ('step_dt', C.c_void_p), ('step_t', C.c_void_p),
                 ('k_jump', C.c_void_p), ('time_ptr', C.c_void_p)]
+
+
+class NjodeProtocolJob(C.Structure):
+    _fields_ = [('pred', C.c_void_p), ('n_rows', C.c_int32), ('B', C.c_int32), ('dim', C.c_int32),
+                ('n_query', C.c_int32), ('rows', C.c_void_p), ('vals', C.c_void_p),
+                ('mask', C.c_void_p), ('X_val', C.c_void_p), ('M_val', C.c_void_p),
+                ('index_val', C.c_void_p)]
 
 
 class NjodeError(RuntimeError):
@@ -171,10 +181,14 @@ def lib():
     L.njode_cond_exp_staged_f64.argtypes = [C.POINTER(NjodeSdeStage), i32, C.POINTER(NjodeBatch),
                                             C.POINTER(NjodeCondExpSchedule), f64, vp, vp, vp, vp,
                                             vp, sz, vp]
+    L.njode_protocol_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
+    L.njode_protocol_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+    L.njode_protocol_score_f32.argtypes = [C.POINTER(NjodeProtocolJob), vp, i32, vp, sz, vp]
     for name in ('njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
                  'njode_collate_count', 'njode_collate_fill',
                  'njode_cond_exp_bytes', 'njode_cond_exp_f64',
                  'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
+                 'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
         getattr(L, name).restype = C.c_int

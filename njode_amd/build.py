@@ -138,6 +138,7 @@ def build(force=False, jobs=None, verbose=True):
     hdr = os.path.join(os.path.dirname(HERE), 'include', 'njode_hip.h')
     hdr_prod = os.path.join(os.path.dirname(HERE), 'include', 'njode_producer.h')
     hdr_self = os.path.join(os.path.dirname(HERE), 'include', 'njode_selftest.h')
+    hdr_proto = os.path.join(os.path.dirname(HERE), 'include', 'njode_protocol.h')
     kernel_deps = [os.path.join(CSRC, n) for n in
                    ('njode_cfg.hip', 'njode_host.h', 'njode_kernels.h', 'njode_device.h',
                     'njode_mfma.h', 'njode_mfma_rows.h', 'njode_lockstep_bwd.h',
@@ -157,6 +158,8 @@ def build(force=False, jobs=None, verbose=True):
         hdr, hdr_prod]
     ce_deps = [os.path.join(CSRC, n) for n in ('njode_condexp.hip', 'njode_error.h')] + [
         hdr, hdr_prod]
+    proto_deps = [os.path.join(CSRC, n) for n in ('njode_protocol.hip', 'njode_error.h')] + [
+        hdr, hdr_proto]
     tasks = []   # (object, command, digest)
     for i, (d, h, do, nh, w, act, masked, curt, res, rnn) in enumerate(cfgs):
         for part in range(6):
@@ -182,6 +185,10 @@ def build(force=False, jobs=None, verbose=True):
     ce_obj = os.path.join(OBJ, 'condexp.o')
     cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_condexp.hip'), '-o', ce_obj]
     tasks.append((ce_obj, cmd, _digest(ce_deps, ' '.join(cmd))))
+    # ... and the evaluation protocols (numpy's fp32 terms: subtract, square, multiply, unfused)
+    proto_obj = os.path.join(OBJ, 'protocol.o')
+    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_protocol.hip'), '-o', proto_obj]
+    tasks.append((proto_obj, cmd, _digest(proto_deps, ' '.join(cmd))))
     if os.environ.get('NJODE_RESTAMP'):   # maintainer aid: adopt the objects on disk as current
         for t in tasks:
             if os.path.exists(t[0]):
@@ -196,7 +203,7 @@ def build(force=False, jobs=None, verbose=True):
     todo = [t for t in tasks if stale(t)]
     parts_only = os.environ.get('NJODE_PARTS_ONLY', '').strip()   # maintainer aid, e.g. "0": a change
     if parts_only:                                                 # that only touches those parts
-        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'gen.o')
+        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'protocol.o', 'gen.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
                 with open(t[0] + '.stamp', 'w') as f:

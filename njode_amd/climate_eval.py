@@ -119,3 +119,68 @@ def evaluate_model(model, batches, device, delta_t, T):
             loss_val += float(e_loss.detach().cpu())
             num_obs += float(M_val.sum())
         return loss_val / len(batches), mse_val / num_obs
+
+
+def _check_batch(b):
+    """What ``evaluate_model_device`` refuses about a batch before anything is launched: the
+    held-out arrays as fp32 numpy, the times as float64, ``index_val`` as int32."""
+    from . import protocol
+    B, dim = len(b['pat_idx']), int(b['X'].shape[1])
+    times_val = np.asarray(b['times_val'], dtype=np.float64)
+    if times_val.ndim != 1:
+        raise ValueError('times_val must be a vector')
+    L = len(times_val)
+    X_val = protocol.as_f32('X_val', b['X_val'], (L, dim))
+    M_val = protocol.as_f32('M_val', b['M_val'], (L, dim))
+    index_val = b['index_val']
+    index_val = index_val.detach().cpu().numpy() if torch.is_tensor(index_val) else np.asarray(index_val)
+    if index_val.dtype.kind not in 'iu':
+        raise ValueError('index_val must hold integers, not {}'.format(index_val.dtype))
+    if index_val.shape != (L,):
+        raise ValueError('index_val must be [{}], not {}'.format(L, list(index_val.shape)))
+    if L and (index_val.min() < 0 or index_val.max() >= B):
+        raise ValueError('index_val must lie in [0, {}): found {} and {}'.format(
+            B, int(index_val.min()), int(index_val.max())))
+    return X_val, M_val, times_val, np.ascontiguousarray(index_val, dtype=np.int32)
+
+
+def evaluate_model_device(model, batches, device, delta_t, T):
+    """``evaluate_model`` without leaving the GPU: the same batches, the same model call and the
+    same pair ``(loss_val, mse_val)``.  The prediction path stays in device memory: the rows
+    ``extract_from_path`` would select are found there (``protocol.rows``; ``path_t`` is rounded
+    and cast through float32 on the host, as above), the masked squared errors are summed there in
+    float64 (``protocol.score``) and accumulate there over the batches together with the loss;
+    the host reads four doubles and the loss once, after the last batch.  With
+    ``options['device_outputs']`` nothing in the loop waits for the device.
+
+    ``ValueError``, before anything is launched: an ``index_val`` outside ``[0, B)`` or not of an
+    integer type, held-out arrays whose shapes disagree with the batch or each other, a ``device``
+    that is not a GPU.  ``ZeroDivisionError`` if no held-out entry was observed, like the host
+    arithmetic."""
+    from . import protocol
+    dev = protocol.need_cuda_device(device)
+    checked = [_check_batch(b) for b in batches]
+    f64 = torch.float64
+    with torch.no_grad():
+        model.eval()
+        acc = torch.zeros(5, dtype=f64, device=dev)      # sq_sum, n_obs, (unused), 0 | loss
+        for b, (X_val, M_val, times_val, index_val) in zip(batches, checked):
+            b_size = len(b['pat_idx'])
+            X = b['X'].to(dev)
+            M = b['M'].to(dev)
+            obs_idx = b['obs_idx'].to(dev)
+            n_obs_ot = torch.bincount(obs_idx, minlength=b_size)
+            start_X = torch.zeros(b_size, X.shape[1], dtype=torch.float32, device=dev)
+            _, e_loss, path_t, _, path_y = model(
+                b['times'], b['time_ptr'], X, obs_idx, delta_t, T, start_X, n_obs_ot,
+                until_T=True, return_path=True, get_loss=True, M=M)
+            # round the floating point error out of the time vector (reference :549-551)
+            t_vec = np.around(path_t, n_decimals(delta_t)).astype(np.float32).astype(np.float64)
+            ind = protocol.rows(torch.from_numpy(t_vec).to(dev), torch.from_numpy(times_val).to(dev),
+                                'first_nearest')
+            protocol.score(path_y, ind, X_val=torch.from_numpy(X_val).to(dev),
+                           M_val=torch.from_numpy(M_val).to(dev),
+                           index_val=torch.from_numpy(index_val).to(dev), out=acc[:4], accumulate=True)
+            acc[4] += e_loss.detach().to(device=dev, dtype=f64)
+        sq_sum, num_obs, _, _, loss_val = acc.cpu().tolist()
+        return loss_val / len(batches), sq_sum / num_obs

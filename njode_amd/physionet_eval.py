@@ -119,3 +119,63 @@ def evaluate_model(model, batches, device, delta_t, T):
             count += 1
             mse_val_2 += masked_mse_per_attribute(path_y, b['vals_val'], b['mask_val'])
         return loss_val / count, mse_val / num_obs, mse_val_2 / count
+
+
+def _check_batch(model, b, delta_t, T):
+    """What ``evaluate_model_device`` refuses about a batch before anything is launched: the
+    held-out arrays as fp32 numpy, the times as float64 and the ``path_t`` of the call."""
+    from . import protocol
+    B, dim = int(b['batch_size']), int(b['X'].shape[1])
+    times_val = np.asarray(b['times_val'], dtype=np.float64)
+    if times_val.ndim != 1 or times_val.size == 0:
+        raise ValueError('times_val must be a non-empty vector')
+    shape = (B, len(times_val), dim)
+    vals = protocol.as_f32('vals_val', b['vals_val'], shape)
+    mask = protocol.as_f32('mask_val', b['mask_val'], shape)
+    path_t = protocol.model_path_t(model, b['times'], delta_t, T)
+    # the range check of get_comparison_times_ind
+    assert np.min(path_t) < np.min(times_val) and np.max(path_t) + 1e-10 > np.max(times_val), \
+        "mins: {}, {}, max: {}, {}".format(np.min(path_t), np.min(times_val), np.max(path_t),
+                                           np.max(times_val))
+    return vals, mask, times_val, path_t
+
+
+def evaluate_model_device(model, batches, device, delta_t, T):
+    """``evaluate_model`` without leaving the GPU: the same batches, the same model call and the
+    same triple ``(loss_val, mse_val, mse_val_2)``.  The prediction path stays in device memory:
+    the rows that answer ``times_val`` are found there (``protocol.rows``), the masked squared
+    errors are summed there in float64 (``protocol.score``; ``mse_val_2`` is taken in float64
+    instead of fp32) and accumulate there over the batches together with the loss; the host
+    reads four doubles and the loss once, after the last batch.  ``n_obs_ot`` is a device
+    ``bincount``, the held-out arrays are uploaded once per batch.  With
+    ``options['device_outputs']`` nothing in the loop waits for the device.
+
+    Before anything is launched: the ``AssertionError`` of ``get_comparison_times_ind``'s range
+    check (same message); ``ValueError`` for held-out arrays whose shapes disagree with the
+    batch and for a ``device`` that is not a GPU.  ``ZeroDivisionError`` if no held-out entry was
+    observed, like the host arithmetic."""
+    from . import protocol
+    dev = protocol.need_cuda_device(device)
+    checked = [_check_batch(model, b, delta_t, T) for b in batches]
+    f64 = torch.float64
+    with torch.no_grad():
+        model.eval()
+        acc = torch.zeros(5, dtype=f64, device=dev)      # sq_sum, n_obs, attr_mse, 0 | loss
+        for b, (vals, mask, times_val, _) in zip(batches, checked):
+            b_size = b['batch_size']
+            X = b['X'].to(dev)
+            M = b['M'].to(dev)
+            obs_idx = b['obs_idx'].to(dev)
+            n_obs_ot = torch.bincount(obs_idx, minlength=b_size)
+            start_X = torch.zeros(b_size, X.shape[1], dtype=torch.float32, device=dev)
+            _, e_loss, path_t, _, path_y = model(
+                b['times'], b['time_ptr'], X, obs_idx, delta_t, T, start_X, n_obs_ot,
+                until_T=True, return_path=True, get_loss=True, M=M)
+            ind = protocol.rows(torch.from_numpy(np.asarray(path_t, dtype=np.float64)).to(dev),
+                                torch.from_numpy(times_val).to(dev), 'closest')
+            protocol.score(path_y, ind, vals=torch.from_numpy(vals).to(dev),
+                           mask=torch.from_numpy(mask).to(dev), out=acc[:4], accumulate=True)
+            acc[4] += e_loss.detach().to(device=dev, dtype=f64)
+        sq_sum, num_obs, attr, _, loss_val = acc.cpu().tolist()
+        count = len(batches)
+        return loss_val / count, sq_sum / num_obs, attr / count
