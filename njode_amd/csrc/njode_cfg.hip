@@ -180,8 +180,7 @@ template <class CC, bool DROP> static void launch_ode_bwd_mfma(const KArgs& a, c
     if constexpr (HAS_SPLIT) {
       if (r.ode_split) {
         ProfScope ps("k_ode_bwd_mixed", st);
-        if (r.tile_q_on) k_ode_bwd_mixed<CC, DROP, true><<<a.n_blocks_bwd, 256, 0, st>>>(a);
-        else k_ode_bwd_mixed<CC, DROP, false><<<a.n_blocks_bwd, 256, 0, st>>>(a);
+        k_ode_bwd_mixed<CC, DROP><<<a.n_blocks_bwd, 256, 0, st>>>(a);
         return;
       }
     }
@@ -223,12 +222,9 @@ static void launch_mfma_fwd(const KArgs& a, const Route& r, hipStream_t st) {
         else if (a.plan_job) {
           // the next batch's plan rides in front of this launch's own blocks (njode_plan.h)
           const PlanJob job = *(const PlanJob*)a.plan_job;
-          // (never with NJODE_ENC_FUSED: that variant is two registers over the three-waves-per-SIMD
-          // limit once it carries the plan; njode_api.hip launches the plan in front of such a call)
-          k_ode_fwd_mixed_plan<CC, DROP, false><<<a.n_blocks_fwd + job.P, 256, 0, st>>>(a, job);
+          k_ode_fwd_mixed_plan<CC, DROP><<<a.n_blocks_fwd + job.P, 256, 0, st>>>(a, job);
         }
-        else if (r.enc_fused) k_ode_fwd_mixed<CC, DROP, true><<<a.n_blocks_fwd, 256, 0, st>>>(a);
-        else k_ode_fwd_mixed<CC, DROP, false><<<a.n_blocks_fwd, 256, 0, st>>>(a);
+        else k_ode_fwd_mixed<CC, DROP><<<a.n_blocks_fwd, 256, 0, st>>>(a);
         return;
       }
     }
@@ -245,9 +241,7 @@ template <bool DROP, bool TAIL, int ODE> static void launch_ode_fwd(const KArgs&
   if constexpr (ODE == ODE_MFMA) {
     launch_mfma_fwd<C, DROP, TAIL>(a, r, st);
   } else {
-    constexpr bool WLDS = ODE == ODE_VALU_LDS;
-    constexpr int NT = WLDS ? 256 : 64;
-    k_ode_fwd_items<C, DROP, TAIL, WLDS><<<cdiv(n_items, NT), NT, 0, st>>>(a);
+    k_ode_fwd_items<C, DROP, TAIL><<<cdiv(n_items, 64), 64, 0, st>>>(a);
   }
 }
 template <bool DROP, int ODE>
@@ -270,7 +264,7 @@ static hipError_t seg_forward_t(const KArgs& a, const Route& r, hipStream_t st) 
       ProfScope ps("k_pack_all", s2);
       launch_pack_frags<C>(ab, s2, r.seg_bits_ahead);
     }
-    if (!r.enc_fused) {
+    {
       ProfScope ps(ODE == ODE_MFMA ? "k_encode_rows_mfma" : "k_encode_rows", s2);
       if constexpr (ODE == ODE_MFMA) launch_mfma_enc<C, DROP>(a, r, s2);
       else k_encode_rows<C, DROP><<<cdiv(a.n_obs + a.B, 64), 64, 0, s2>>>(a);
@@ -278,15 +272,6 @@ static hipError_t seg_forward_t(const KArgs& a, const Route& r, hipStream_t st) 
     if (side) {
       (void)hipEventRecord(side->e1, s2);
       (void)hipStreamWaitEvent(st, side->e1, 0);
-    }
-    if constexpr (ODE == ODE_MFMA && HAS_SPLIT) {
-      if (r.enc_fused) {
-        // NJODE_ENC_FUSED: what the ODE forward's one-wave role does not evaluate itself (needs the
-        // plan -- the item order and the split point -- so it runs on `st`, behind it)
-        ProfScope ps("k_encode_rows_items", st);
-        const int n_path_tiles = cdiv(a.B, 16);
-        k_encode_rows_items<C, DROP><<<n_path_tiles + a.n_split_fwd * 4, 64, 0, st>>>(a, n_path_tiles);
-      }
     }
     // the tails (hT: every path from its last observation to the end) need the encoder's outputs
     // and nothing else of this call: with helper streams they start TOGETHER with the items' ODE
@@ -332,11 +317,7 @@ static hipError_t seg_forward_t(const KArgs& a, const Route& r, hipStream_t st) 
 hipError_t NJ_CAT(njode_seg_forward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
   return with_drop(r.drop, [&](auto D) {
     constexpr bool DROP = decltype(D)::value;
-    switch (r.seg_ode) {
-      case ODE_MFMA: return seg_forward_t<DROP, ODE_MFMA>(a, r, st);
-      case ODE_VALU_LDS: return seg_forward_t<DROP, ODE_VALU_LDS>(a, r, st);
-      default: return seg_forward_t<DROP, ODE_VALU>(a, r, st);
-    }
+    return r.seg_ode == ODE_MFMA ? seg_forward_t<DROP, ODE_MFMA>(a, r, st) : seg_forward_t<DROP, ODE_VALU>(a, r, st);
   });
 }
 
@@ -384,8 +365,7 @@ template <bool DROP, int ODE> static hipError_t seg_backward_t(const KArgs& a, c
     }
     {
       ProfScope ps("k_ode_bwd_items", st);
-      if constexpr (ODE == ODE_VALU_LDS) k_ode_bwd_items<C, DROP, true><<<a.n_waves / 4, 256, 0, st>>>(a);
-      else k_ode_bwd_items<C, DROP, false><<<a.n_waves, 64, 0, st>>>(a);
+      k_ode_bwd_items<C, DROP><<<a.n_waves, 64, 0, st>>>(a);
     }
     {
       ProfScope ps("k_encode_rows_bwd", st);
@@ -397,11 +377,7 @@ template <bool DROP, int ODE> static hipError_t seg_backward_t(const KArgs& a, c
 hipError_t NJ_CAT(njode_seg_backward_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) {
   return with_drop(r.drop, [&](auto D) {
     constexpr bool DROP = decltype(D)::value;
-    switch (r.seg_ode) {
-      case ODE_MFMA: return seg_backward_t<DROP, ODE_MFMA>(a, r, st);
-      case ODE_VALU_LDS: return seg_backward_t<DROP, ODE_VALU_LDS>(a, r, st);
-      default: return seg_backward_t<DROP, ODE_VALU>(a, r, st);
-    }
+    return r.seg_ode == ODE_MFMA ? seg_backward_t<DROP, ODE_MFMA>(a, r, st) : seg_backward_t<DROP, ODE_VALU>(a, r, st);
   });
 }
 #endif

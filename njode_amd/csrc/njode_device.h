@@ -243,8 +243,7 @@ NJ_DEV void wave_lds_sync() {
 // padded to 16 B so every lane reads its operands with ds_read_b128; the row
 // stride is an odd number of 16-B slots, so the ds_write_b128 of consecutive
 // lanes (rows) hit distinct banks.
-// CH = chains staged per phase (64 / CH phases per wave): 32 by default, 16 where the
-// weights share the LDS with the staging rows.
+// CH = chains staged per phase (64 / CH phases per wave): 32.
 
 template <int N_, int K_, int CH_ = 32> struct Tile {
   static constexpr int N = N_, K = K_, CH = CH_;

@@ -12,8 +12,8 @@ namespace njode {
 
 constexpr int MAX_WAVES = 2048;
 // ODE-evolve implementations: matrix cores (default where compiled), VALU with weights
-// through the scalar cache, VALU with LDS-staged weights
-constexpr int ODE_MFMA = 0, ODE_VALU = 1, ODE_VALU_LDS = 2;
+// through the scalar cache
+constexpr int ODE_MFMA = 0, ODE_VALU = 1;
 // (NJODE_ODE=mfma1 keeps ODE_MFMA but with one wave per tile, njode_mfma.h, where the default
 // picks the mixed kernels of njode_mfma_split.h: A/B baseline)
 

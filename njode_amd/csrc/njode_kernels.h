@@ -124,10 +124,12 @@ struct KArgs {
   float* loss_terms;
   float* slab;
   float* trash;  // [64 * max(H, D)] scratch target for the stores of inactive lanes
-  // tile queue of the mixed ODE backward (njode_ode2.h): [0] four-wave tiles, [1] bulk tiles,
-  // [2] finished blocks; tile_q_on: this launch pops its tiles (else static snake rounds)
-  int* tile_q;
-  int tile_q_on;
+  // the barrier counters (8 words) of the plan job this call's ODE forward hosts, when the fragment-pack
+  // launch in front of it zeroes them (same stream: no memset launch of their own); else null
+  unsigned* plan_sync_zero;
+  // (reserved, unused: keeps every field below at its measured offset modulo 16, by which the compiler merges the
+  // kernels' argument loads; without it k_jump_rows_bwd_mfma spills 10 VGPRs, not 6: profiles/retired_variants_*.txt)
+  int args_pad;
   int n_waves;      // persistent gradient kernels (VALU): waves == slab rows
   int n_waves_ode;  // same for the ODE backward kernel
   int n_waves_rows; // same for the row backward kernels on the matrix cores
@@ -170,12 +172,6 @@ struct KArgs {
   long long* tile_last;
   int dw_pair_blocks, dw_seg_blocks;
   int dw_enc_fused;   // segment plan: k_encode_rows_bwd_mfma rides in that launch (njode_chain_dw.h)
-  // the barrier counters (8 words) of the plan job this call's ODE forward hosts, when the fragment-pack
-  // launch in front of it zeroes them (same stream: no memset launch of their own); else null
-  unsigned* plan_sync_zero;
-  // segment plan, round 5 (NJODE_ENC_FUSED=1): the one-wave role of k_ode_fwd_mixed evaluates
-  // encoder(X) of an item's START row itself (njode_ode2.h); k_encode_rows_items covers the rest
-  int enc_fused;
   DropCtx dc;
   float keep;
 };
@@ -450,21 +446,14 @@ template <class C> struct Item {
 };
 
 // B: Euler evolve of every item from its h0 to the state just before its jump (or, for
-// tail items, to the end of the schedule).  WLDS: the ODE network's weights are staged
-// in LDS once per 256-thread block and read with wave-uniform ds_reads; otherwise they
-// come through the scalar cache (s_load).
-template <class C, bool DROP, bool TAIL, bool WLDS>
-__global__ void __launch_bounds__(WLDS ? 256 : 64) k_ode_fwd_items(KArgs a) {
+// tail items, to the end of the schedule).  The ODE network's weights come through the
+// scalar cache (s_load).
+template <class C, bool DROP, bool TAIL>
+__global__ void __launch_bounds__(64) k_ode_fwd_items(KArgs a) {
   const bool SAVE = !TAIL && a.save_traj != 0;  // wave-uniform
-  constexpr int NT = WLDS ? 256 : 64;
   using NL = typename C::Ode;
-  __shared__ __attribute__((aligned(16))) float wl[WLDS ? NL::SIZE : 4];
-  if constexpr (WLDS) {
-    for (int i = threadIdx.x; i < NL::SIZE; i += NT) wl[i] = a.P[C::OFF_ODE + i];
-    __syncthreads();
-  }
   const int n_items = TAIL ? a.B : a.n_obs;
-  const int j = blockIdx.x * NT + threadIdx.x;
+  const int j = blockIdx.x * 64 + threadIdx.x;
   const bool valid = j < n_items;
   Item<C> it;
   it.template load<TAIL>(a, j, valid);
@@ -484,11 +473,7 @@ __global__ void __launch_bounds__(WLDS ? 256 : 64) k_ode_fwd_items(KArgs a) {
     ode_input<C>(it.tx, h, it.tau, t, in0);
     Masks<C, DROP> mk;
     mk.draw(a, a.gid0 + it.b, (uint32_t)k, NET_ODE);
-    if constexpr (WLDS)
-      net_fwd<NL, C::ACT, DROP>((lcp)wl, in0, f, a1, a2, mk.m1, mk.m2, a.dc.inv_keep);
-    else
-      net_fwd<NL, C::ACT, DROP>(as_cfp(a.P) + C::OFF_ODE, in0, f, a1, a2, mk.m1, mk.m2,
-                                a.dc.inv_keep);
+    net_fwd<NL, C::ACT, DROP>(as_cfp(a.P) + C::OFF_ODE, in0, f, a1, a2, mk.m1, mk.m2, a.dc.inv_keep);
 #pragma unroll
     for (int i = 0; i < C::H; ++i) h[i] = fmaf(dt, f[i], h[i]);  // dt == 0 when inactive
   }
@@ -591,28 +576,16 @@ __global__ void __launch_bounds__(64, 2) k_jump_rows_bwd(KArgs a) {
 }
 
 // C: reverse Euler sweep of every segment (exact discrete adjoint), d loss / d ODE params.
-// WLDS: weights (W and its transposed copy) staged in LDS once per 256-thread block
-// (4 waves, each with its own staging rows, 16 chains per phase).
-template <class C, bool DROP, bool WLDS>
-__global__ void __launch_bounds__(WLDS ? 256 : 64, 2) k_ode_bwd_items(KArgs a) {
+template <class C, bool DROP>
+__global__ void __launch_bounds__(64, 2) k_ode_bwd_items(KArgs a) {
   using NL = typename C::Ode;
-  constexpr int CHN = WLDS ? 16 : 32;
-  constexpr int NW = WLDS ? 4 : 1, NT = NW * 64;
+  constexpr int CHN = 32;
+  constexpr int NW = 1;
   using Acc = NetAcc<NL, CHN>;
-  __shared__ __attribute__((aligned(16))) float
-      lds_raw[NW * Acc::LDS_FLOATS + (WLDS ? 2 * NL::SIZE : 0)];
+  __shared__ __attribute__((aligned(16))) float lds_raw[NW * Acc::LDS_FLOATS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wave = blockIdx.x * NW + wv;
   lfp lds = (lfp)lds_raw + wv * Acc::LDS_FLOATS;
-  if constexpr (WLDS) {
-    float* wl = lds_raw + NW * Acc::LDS_FLOATS;
-    for (int i = threadIdx.x; i < NL::SIZE; i += NT) {
-      wl[i] = a.P[C::OFF_ODE + i];
-      wl[NL::SIZE + i] = a.PT[C::OFF_ODE + i];
-    }
-    __syncthreads();
-  }
-  const lcp Wl = (lcp)(lds_raw + NW * Acc::LDS_FLOATS), WTl = Wl + NL::SIZE;
   const cfp Ws = as_cfp(a.P) + C::OFF_ODE, WTs = as_cfp(a.PT) + C::OFF_ODE;
   Acc g;
   g.zero();
@@ -640,19 +613,12 @@ __global__ void __launch_bounds__(WLDS ? 256 : 64, 2) k_ode_bwd_items(KArgs a) {
       ode_input<C>(it.tx, h, it.tau, t, in0);
       Masks<C, DROP> mk;
       mk.draw(a, a.gid0 + it.b, (uint32_t)k, NET_ODE);
-      if constexpr (WLDS)
-        net_fwd<NL, C::ACT, DROP>(Wl, in0, f, a1, a2, mk.m1, mk.m2, a.dc.inv_keep);
-      else
-        net_fwd<NL, C::ACT, DROP>(Ws, in0, f, a1, a2, mk.m1, mk.m2, a.dc.inv_keep);
+      net_fwd<NL, C::ACT, DROP>(Ws, in0, f, a1, a2, mk.m1, mk.m2, a.dc.inv_keep);
       // h' = h + dt f(h): d/df = dt * lam (zero for inactive lanes since dt = 0)
 #pragma unroll
       for (int i = 0; i < C::H; ++i) dout[i] = dt * lam[i];
-      if constexpr (WLDS)
-        net_bwd<NL, C::ACT, DROP, C::D, C::D + C::H>(WTl, lds, g, in0, dout, a1, a2, mk.m1,
-                                                     mk.m2, a.dc.inv_keep, a.keep, din, lane);
-      else
-        net_bwd<NL, C::ACT, DROP, C::D, C::D + C::H>(WTs, lds, g, in0, dout, a1, a2, mk.m1,
-                                                     mk.m2, a.dc.inv_keep, a.keep, din, lane);
+      net_bwd<NL, C::ACT, DROP, C::D, C::D + C::H>(WTs, lds, g, in0, dout, a1, a2, mk.m1,
+                                                   mk.m2, a.dc.inv_keep, a.keep, din, lane);
 #pragma unroll
       for (int i = 0; i < C::H; ++i) {
         const float th = in0[C::D + i];

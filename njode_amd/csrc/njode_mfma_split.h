@@ -399,7 +399,7 @@ NJ_DEV void ode_fwd_split(const KArgs& a, lfp lds_raw, int worker, int n_workers
 // shared: X1 (a1 / its image), X2 (d2 / its image), reduce buffer; per wave: images of d3,
 // own a2 tile, own d1 tile, b0
 template <class C> struct OdeBwdSplitLds {
-  static constexpr int FLOATS = 2 * XFLOATS + 4 * MF<C>::QH * 64 + 4 * 4 * TFLOATS + 64;   // (+ the tile queue's hand-over word)
+  static constexpr int FLOATS = 2 * XFLOATS + 4 * MF<C>::QH * 64 + 4 * 4 * TFLOATS;
 };
 // C (split): reverse Euler sweep, d loss / d ODE params.  Block `worker` of `n_workers` walks
 // the tiles [tile0, tile1); one slab row per block, wave w flushes the tiles it owns.
@@ -587,11 +587,9 @@ template <class C> struct SplitFragsT {
 };
 
 // C (split, stored activations): as ode_bwd_split, the hidden activations loaded
-// QUEUE (njode_ode2.h, tile queue): the block pops tiles [tile0, tile1) from tile_q[0], then -- a
-// four-wave block runs any tile -- helps with the bulk's [tile1, n_all) from tile_q[1]
-template <class C, bool DROP, bool QUEUE = false>
+template <class C, bool DROP>
 NJ_DEV void ode3_bwd_split(const KArgs& a, lfp lds_raw, int worker, int n_workers, int tile0, int tile1,
-                          int slab_row, int n_all = 0) {
+                          int slab_row) {
   using M = MF<C>;
   using NL = typename C::Ode;
   constexpr int NT1 = 4;
@@ -614,44 +612,11 @@ NJ_DEV void ode3_bwd_split(const KArgs& a, lfp lds_raw, int worker, int n_worker
   float* const trash = a.trash + lane * C::H;
   const int n_tiles = tile1 - tile0;
   BWD_STAMP(1, wall_clock64());
-  // (QUEUE: wave 0 pops -- one tile ahead, so the atomic's round trip hides behind the sweep -- and
-  // hands the tile to the block through one LDS word)
-  int __attribute__((address_space(3)))* qword = (int __attribute__((address_space(3)))*)(lds_raw + OdeBwdSplitLds<C>::FLOATS - 64);
-  // (QUEUE) wave 0 pops: first tile = the block's own index (static, no burst at launch), then
-  // tile_q[0] counts on from n_workers through [tile0, tile1), then tile_q[1] from the bulk's
-  // worker count through [tile1, n_all); the pop for the NEXT tile is issued, unwaited, when a
-  // tile's prologue is done and read one tile later (njode_ode2.h, queue_pop_issue)
-  const int n_bulk_workers = QUEUE ? ((int)gridDim.x - n_workers) * 4 : 0;
-  int q_phase = 0, q_raw = 0;
-  auto resolve = [&](int raw) -> int {          // tile of a returned pop; may need a second pop
-    if (q_phase == 0) {
-      const int t = n_workers + queue_value(raw);
-      if (t < n_tiles) return tile0 + t;
-      q_phase = 1;
-      return tile1 + n_bulk_workers + queue_value(queue_pop_issue(a.tile_q + 1));
-    }
-    return tile1 + n_bulk_workers + queue_value(raw);
-  };
-  int q_next = 0;
-  if constexpr (QUEUE) {
-    if (worker < n_tiles) q_next = tile0 + worker;
-    else { q_phase = 1; if (w == 0) q_next = tile1 + n_bulk_workers + queue_value(queue_pop_issue(a.tile_q + 1)); }
-  }
   int n_done = 0, n_steps_done = 0;
-  for (int round = 0; QUEUE || round * n_workers < n_tiles; ++round) {
-    int tile;
-    if constexpr (QUEUE) {
-      if (round > 0 && w == 0) q_next = resolve(q_raw);
-      if (w == 0 && lane == 0) *qword = q_next;
-      block_lds_barrier();
-      tile = uniform(*qword);
-      block_lds_barrier();
-      if (tile >= n_all) break;
-    } else {
-      const int rel = snake_tile(round, worker, n_workers);
-      if (rel >= n_tiles) continue;
-      tile = tile0 + rel;
-    }
+  for (int round = 0; round * n_workers < n_tiles; ++round) {
+    const int rel = snake_tile(round, worker, n_workers);
+    if (rel >= n_tiles) continue;
+    const int tile = tile0 + rel;
     const int j = tile * 16 + c;
     const bool valid = j < a.n_obs;
     Item<C> it;
@@ -678,7 +643,6 @@ NJ_DEV void ode3_bwd_split(const KArgs& a, lfp lds_raw, int worker, int n_worker
     };
     if (nmax > 0) fetch(nmax - 1);
     vm_drain();
-    if constexpr (QUEUE) { if (w == 0) q_raw = queue_pop_issue(a.tile_q + (q_phase == 0 ? 0 : 1)); }
     for (int s = nmax - 1; s >= 0; --s) {
       float h[M::QH], a1u[4], a2u[4];
       nx.unpack(w, a1u, a2u, h);
@@ -811,23 +775,18 @@ __global__ void __launch_bounds__(256, 2) k_ode_fwd_split(KArgs a) {
 // of their own (higher throughput per SIMD).  T balances the two groups' finishing times,
 // so the long segments no longer set the kernel time and the bulk still runs at the
 // single-wave kernels' rate.
-// (ENC: the NJODE_ENC_FUSED=1 form -- a kernel of its own, so that the default one keeps its
-// registers and its LDS footprint)
 // (PLAN: the launch carries the NEXT batch's plan in front of its own blocks -- njode_plan.h; a
 // kernel of its own, so that launches without a job keep their argument list and their registers)
-template <class C, bool ENC, bool PLAN> struct OdeFwdMixedLds {
-  static constexpr int OWN = OdeFwdSplitLds<C>::FLOATS + (ENC ? EncFwdLds<C>::FLOATS : 0);
+template <class C, bool PLAN> struct OdeFwdMixedLds {
+  static constexpr int OWN = OdeFwdSplitLds<C>::FLOATS;
   static constexpr int FLOATS = (PLAN && PLAN_LDS_INTS > OWN) ? PLAN_LDS_INTS : OWN;
 };
-template <class C, bool DROP, bool ENC, bool PLAN>
+template <class C, bool DROP, bool PLAN>
 __device__ __forceinline__ void ode_fwd_mixed_body(const KArgs& a, lfp lds_raw, int bid, int nblocks) {
   const int n_tiles = (a.n_obs + 15) / 16, ns = a.n_split_fwd;
   const int T = (int)a.base_s[a.K + 2];
   const bool save = a.save_traj != 0;   // wave-uniform: a training forward stores checkpoints
                                          // and activations, an evaluation forward nothing
-  // (the backward's tile queue starts from zero: its last block clears it again, this covers the
-  // very first launch on a fresh workspace)
-  if (save && bid == 0 && threadIdx.x == 0) { a.tile_q[0] = 0; a.tile_q[1] = 0; a.tile_q[2] = 0; }
   if (bid < ns) {
     if (save) ode_fwd_split<C, DROP, false, true>(a, lds_raw, bid, ns, 0, T);
     else ode_fwd_split<C, DROP, false, false>(a, lds_raw, bid, ns, 0, T);
@@ -835,41 +794,30 @@ __device__ __forceinline__ void ode_fwd_mixed_body(const KArgs& a, lfp lds_raw, 
     const int wave = (bid - ns) * 4 + uniform(threadIdx.x >> 6);
     // one-wave role on the scaled fragments (njode_ode2.h): same masks, same values to rounding
     const int nw = (nblocks - ns) * 4;
-    if constexpr (ENC) {   // the wave evaluates the encoder at the head of every item
-      lfp enc_img = lds_raw + OdeFwdSplitLds<C>::FLOATS;
-      EncFwdLds<C>::stage(enc_img, a.frag_enc, threadIdx.x, 256);
-      __syncthreads();
-      if (save) ode2_fwd_single<C, DROP, false, true, true>(a, threadIdx.x & 63, wave, nw, T, n_tiles, enc_img);
-      else ode2_fwd_single<C, DROP, false, false, true>(a, threadIdx.x & 63, wave, nw, T, n_tiles, enc_img);
-    } else {
-      if (save) ode2_fwd_single<C, DROP, false, true>(a, threadIdx.x & 63, wave, nw, T, n_tiles);
-      else ode2_fwd_single<C, DROP, false, false>(a, threadIdx.x & 63, wave, nw, T, n_tiles);
-    }
+    if (save) ode2_fwd_single<C, DROP, false, true>(a, threadIdx.x & 63, wave, nw, T, n_tiles);
+    else ode2_fwd_single<C, DROP, false, false>(a, threadIdx.x & 63, wave, nw, T, n_tiles);
   }
 }
-template <class C, bool DROP, bool ENC = false>
+template <class C, bool DROP>
 __global__ void __launch_bounds__(256, 2) k_ode_fwd_mixed(KArgs a) {
-  // (ENC: behind the four-wave role's exchange images, the encoder's forward fragments)
-  __shared__ __attribute__((aligned(16))) float lds_raw[OdeFwdMixedLds<C, ENC, false>::FLOATS];
-  ode_fwd_mixed_body<C, DROP, ENC, false>(a, (lfp)lds_raw, blockIdx.x, gridDim.x);
+  __shared__ __attribute__((aligned(16))) float lds_raw[OdeFwdMixedLds<C, false>::FLOATS];
+  ode_fwd_mixed_body<C, DROP, false>(a, (lfp)lds_raw, blockIdx.x, gridDim.x);
 }
-template <class C, bool DROP, bool ENC = false>
+template <class C, bool DROP>
 __global__ void __launch_bounds__(256, 2) k_ode_fwd_mixed_plan(KArgs a, PlanJob job) {
-  __shared__ __attribute__((aligned(16))) float lds_raw[OdeFwdMixedLds<C, ENC, true>::FLOATS];
+  __shared__ __attribute__((aligned(16))) float lds_raw[OdeFwdMixedLds<C, true>::FLOATS];
   if ((int)blockIdx.x < job.P) {
     plan_grid_body(job, blockIdx.x, (int*)lds_raw);
     return;
   }
-  ode_fwd_mixed_body<C, DROP, ENC, true>(a, (lfp)lds_raw, (int)blockIdx.x - job.P, (int)gridDim.x - job.P);
+  ode_fwd_mixed_body<C, DROP, true>(a, (lfp)lds_raw, (int)blockIdx.x - job.P, (int)gridDim.x - job.P);
 }
 template <class C> struct OdeBwdMixedLds {
   static constexpr int A = OdeBwdActLds<C>::FLOATS, B = OdeBwdSplitLds<C>::FLOATS;
   static constexpr int FLOATS = A > B ? A : B;
 };
 // one slab row per block
-// (QUEUE: the NJODE_BWD_QUEUE=1 form -- a kernel of its own: in one kernel with the static rounds its
-// extra live values pushed the register allocation of BOTH over the edge: 256 VGPRs + 75 spilled)
-template <class C, bool DROP, bool QUEUE = false>
+template <class C, bool DROP>
 __global__ void __launch_bounds__(256, 2) k_ode_bwd_mixed(KArgs a) {
   __shared__ __attribute__((aligned(16))) float lds_raw[OdeBwdMixedLds<C>::FLOATS];
   const int n_tiles = (a.n_obs + 15) / 16, ns = a.n_split_blocks;
@@ -883,21 +831,11 @@ __global__ void __launch_bounds__(256, 2) k_ode_bwd_mixed(KArgs a) {
   BWD_STAMP(7, (unsigned long long)((int)blockIdx.x < ns ? 1 : 0) | ((unsigned long long)T << 8) |
                    ((unsigned long long)gridDim.x << 32));
 #endif
-  if constexpr (QUEUE) {   // tile queue, persistent blocks
-    if ((int)blockIdx.x < ns) {
-      ode3_bwd_split<C, DROP, true>(a, (lfp)lds_raw, blockIdx.x, ns, 0, T, blockIdx.x, n_tiles);
-    } else {
-      const int wave = ((int)blockIdx.x - ns) * 4 + uniform(threadIdx.x >> 6);
-      ode3_bwd_single<C, DROP, true>(a, (lfp)lds_raw, wave, ((int)gridDim.x - ns) * 4, T, n_tiles, blockIdx.x);
-    }
-    queue_block_done(a.tile_q, gridDim.x);
+  if ((int)blockIdx.x < ns) {
+    ode3_bwd_split<C, DROP>(a, (lfp)lds_raw, blockIdx.x, ns, 0, T, blockIdx.x);
   } else {
-    if ((int)blockIdx.x < ns) {
-      ode3_bwd_split<C, DROP>(a, (lfp)lds_raw, blockIdx.x, ns, 0, T, blockIdx.x);
-    } else {
-      const int wave = ((int)blockIdx.x - ns) * 4 + uniform(threadIdx.x >> 6);
-      ode3_bwd_single<C, DROP>(a, (lfp)lds_raw, wave, ((int)gridDim.x - ns) * 4, T, n_tiles, blockIdx.x);
-    }
+    const int wave = ((int)blockIdx.x - ns) * 4 + uniform(threadIdx.x >> 6);
+    ode3_bwd_single<C, DROP>(a, (lfp)lds_raw, wave, ((int)gridDim.x - ns) * 4, T, n_tiles, blockIdx.x);
   }
 }
 

@@ -389,65 +389,15 @@ NJ_DEV void out_layer2(const float (&A3)[MF<C>::MTH][MF<C>::Q1], const float (&a
   }
 }
 
-// start state of an item from the encoder (ENC of ode2_fwd_single): h = encoder_map(X of the
-// start row) + identity path, D-layout; stored as h0row[start row] (start values: h0start[path])
-// for the kernels behind the forward
-// forward fragments of the encoder only (S::NFWD vectors), one copy per block
-template <class C> struct EncFwdLds {
-  using S = typename EncS<C>::type;
-  static constexpr int FLOATS = S::NFWD * 64;
-  static NJ_DEV void stage(lfp img, const float* frag_enc, int tid, int nthreads) {
-    for (int i = tid; i < FLOATS; i += nthreads) img[i] = frag_enc[i];
-  }
-};
-template <class C, bool DROP>
-NJ_DEV void ode2_item_start(const KArgs& a, const Item<C>& it, bool valid, lfp enc_img, int lane,
-                            float (&h)[MF<C>::QH]) {
-  using S = typename EncS<C>::type;
-  static_assert(S::QO == MF<C>::QH && S::MTO == MF<C>::MTH, "encoder output = ODE state");
-  const int g = lane >> 4;
-  const bool is_row = it.prev >= 0;
-  const int pv = is_row ? it.prev : 0;
-  const float* xp = is_row ? a.X + (size_t)pv * C::D : a.start_X + (size_t)it.b * C::D;
-  float b0[S::Q0], a1[S::Q1], a2[S::Q1];
-  enc_input<C, S>(xp, b0, g);
-  uint32_t k1, k2;
-  row_keep_bits<DROP>(a, a.gid0 + it.b, is_row ? (uint32_t)a.k_jump[a.t_of_row[pv]] : TKEY_START, NET_ENC, g,
-                      S::Q1, k1, k2);
-  LdsFrags<S> F;
-  F.init(enc_img, lane);
-  f32x4 out[S::MTO];
-  mnet_fwd<S, C::ACT, DROP>(F, b0, a1, a2, out, k1, k2, a.dc.inv_keep, g);
-  float* const trash = a.trash + lane * C::H;
-  float* dstrow = valid ? (is_row ? a.h0row + (size_t)pv * C::H : a.h0start + (size_t)it.b * C::H) : trash;
-#pragma unroll
-  for (int q = 0; q < S::QO; ++q) {
-    const int u = 4 * q + g;
-    const float v = out[q / 4][q % 4] + enc_residual<C>(xp, u < C::H ? u : 0);
-    h[q] = u < C::H ? v : 0.0f;
-    float* dst = u < C::H ? dstrow + u : trash;
-    *dst = v;
-  }
-}
-
 // B (v2): Euler evolve of every item; worker `wave` of `n_waves` walks the tiles
 // [tile0, tile1) in snake order.  Same contract as ode_fwd_single (njode_mfma.h) with the
 // scaled fragment table a.frag2.
 // SAVE (compile time: checkpoints + activations are stored without a branch, so the compiler
 // can COUNT them -- with a runtime `if` around the stores every `s_waitcnt vmcnt` that waits for
 // the next step's prefetched scalars conservatively also drained the stores: +13 % on the kernel)
-// ENC (round 5, NJODE_ENC_FUSED=1; VERDICT r4 item 4's structural option): an item starts at
-// encoder(X of its start row) -- one encoder evaluation per item -- so the wave evaluates it itself
-// at the head of the item (fragments from the block's LDS image `enc_img`, the S::NFWD forward
-// vectors of the encoder; same matrix instructions, same dropout words as k_encode_rows_mfma: the
-// same numbers) and stores h0row[start row] for the row pass, instead of reading what a separate
-// launch over all rows wrote.  k_encode_rows_items then only covers the start rows of the four-wave
-// role's tiles and every path's LAST row (no item starts there).
-template <class C, bool DROP, bool TAIL, bool SAVE, bool ENC = false>
-NJ_DEV void ode2_fwd_single(const KArgs& a, int lane, int wave, int n_waves, int tile0, int tile1,
-                            lfp enc_img = nullptr) {
+template <class C, bool DROP, bool TAIL, bool SAVE>
+NJ_DEV void ode2_fwd_single(const KArgs& a, int lane, int wave, int n_waves, int tile0, int tile1) {
   static_assert(!(TAIL && SAVE), "tail items are never checkpointed");
-  static_assert(!(TAIL && ENC), "tails read the stored state after their last observation");
   using M = MF<C>;
   const int g = lane >> 4, c = lane & 15;
   Ode2FwdFrags<C> F;
@@ -467,15 +417,11 @@ NJ_DEV void ode2_fwd_single(const KArgs& a, int lane, int wave, int n_waves, int
     Item<C> it;
     it.template load<TAIL>(a, j, valid);
     float h[M::QH];
-    if constexpr (ENC) {
-      ode2_item_start<C, DROP>(a, it, valid, enc_img, lane, h);
-    } else {
-      const float* h0 = it.h0(a);
+    const float* h0 = it.h0(a);
 #pragma unroll
-      for (int q = 0; q < M::QH; ++q) {
-        const int u = 4 * q + g;
-        h[q] = u < C::H ? h0[u < C::H ? u : 0] : 0.0f;
-      }
+    for (int q = 0; q < M::QH; ++q) {
+      const int u = 4 * q + g;
+      h[q] = u < C::H ? h0[u < C::H ? u : 0] : 0.0f;
     }
     // (uniform: the step loop is a scalar loop, base16_s[s] a scalar load; the per-lane
     // schedule values of the next step are loaded one step ahead and carried RAW across the
@@ -714,49 +660,11 @@ NJ_DEV void ode3_flush(const KArgs& a, lfp lds_raw, f32x4 (&G3)[MF<C>::MTH][(MF<
     }
 }
 
-// ---- tile queue (round 5; NJODE_BWD_QUEUE=1, not the default) ----------------------------------
-// The backward's gradient accumulators persist across the tiles of a worker, so its blocks cannot
-// be handed out by the dispatcher as the forward's are: rounds 2-4 give every worker its tiles
-// statically (snake order over 1 024 blocks, two per CU resident: the second half of the blocks
-// starts as first-half blocks retire, and a third of the wave slots' time is idle at the end of
-// the launch).  With the queue the launch is exactly the resident blocks and every worker pops
-// the next tile -- longest first, the tiles are sorted -- from a counter in the workspace:
-// KArgs::tile_q[0] for the tiles [0, T) of the four-wave role, [1] for the bulk [T, n_tiles), [2]
-// counts finished blocks (the last one clears all three for the next launch; the saving forward
-// clears them once, too).  Measured (profiles/r05_bwd_fixed_costs.txt): the idle time goes (34 %
-// -> 6 % of wave time) and the launch gets 0.7 % shorter at 20 000 paths, 5 % longer at 125 000,
-// because the Euler-step loop is bound by the SIMD's pipe: kept as a switch, the static rounds stay the default -- they also keep the
-// gradient bitwise reproducible (with the queue, which tiles meet in one accumulator depends on
-// timing: equal to fp32 summation order only).
-// (the pop is issued WITHOUT a wait -- lane 0's register holds the counter's old value once the
-// atomic has returned; queue_value() reads it when the next tile starts, a whole tile later.
-// profiles/r05_bwd_fixed_costs.txt: waited for at once, the round trip of 1 920 waves popping one
-// address was 4.1 us per tile, and the burst at launch -- every wave popping its first tile at the
-// same instant -- is why the first tile of a worker is static: tile = worker index, pops count on
-// from the number of workers)
-NJ_DEV int queue_pop_issue(int* q) {
-  int t = 0;
-  if ((threadIdx.x & 63) == 0) t = atomicAdd(q, 1);
-  return t;
-}
-NJ_DEV int queue_value(int raw) { return __builtin_amdgcn_readfirstlane(raw); }
-NJ_DEV void queue_block_done(int* tile_q, int n_blocks) {   // call once per block, all threads
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(tile_q + 2, 1) == n_blocks - 1) {
-      tile_q[0] = 0;
-      tile_q[1] = 0;
-      tile_q[2] = 0;
-      __threadfence();
-    }
-  }
-}
 #ifdef NJ_BWD_STAMPS
 // diagnostic build (tools/ubench/bwd_stamps.sh): per wave of k_ode_bwd_mixed the 100 MHz wall
 // clock at kernel entry, after the prologue, after the last tile, after the flush; tiles and
 // Euler steps done; hardware id; role; [8] sum over tiles of (tile start -> first Euler step), [9] of
-// the step loops, [10] of the queue pops
+// the step loops
 __device__ unsigned long long g_bwd_stamps[8192 * 16];
 #define BWD_STAMP(slot, val) \
   do { if ((threadIdx.x & 63) == 0) g_bwd_stamps[(size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (slot)] = (val); } while (0)
@@ -764,7 +672,7 @@ __device__ unsigned long long g_bwd_stamps[8192 * 16];
 #define BWD_STAMP(slot, val) do {} while (0)
 #endif
 
-template <class C, bool DROP, bool QUEUE = false>
+template <class C, bool DROP>
 NJ_DEV void ode3_bwd_single(const KArgs& a, lfp lds_raw, int wave, int n_waves, int tile0, int tile1,
                             int slab_row) {
   using M = MF<C>;
@@ -806,23 +714,16 @@ NJ_DEV void ode3_bwd_single(const KArgs& a, lfp lds_raw, int wave, int n_waves, 
   float* const trash = a.trash + threadIdx.x * C::H;
   const int n_tiles = tile1 - tile0;
   BWD_STAMP(1, wall_clock64());
-  int q_raw = 0;                        // (QUEUE) the pending pop: the tile after this one
-  int q_rel = wave;                     // the first tile of a worker is static
   int n_done = 0, n_steps_done = 0;
 #ifdef NJ_BWD_STAMPS
-  unsigned long long t_pro = 0, t_loop = 0, t_pop = 0;
+  unsigned long long t_pro = 0, t_loop = 0;
 #endif
-  for (int round = 0; QUEUE ? q_rel < n_tiles : round * n_waves < n_tiles; ++round) {
+  for (int round = 0; round * n_waves < n_tiles; ++round) {
 #ifdef NJ_BWD_STAMPS
     const unsigned long long tt0 = wall_clock64();
 #endif
-    int rel;
-    if constexpr (QUEUE) {
-      rel = q_rel;
-    } else {
-      rel = snake_tile(round, wave, n_waves);
-      if (rel >= n_tiles) continue;
-    }
+    const int rel = snake_tile(round, wave, n_waves);
+    if (rel >= n_tiles) continue;
     const int tile = tile0 + rel;
     const int j = tile * 16 + c;
     const bool valid = j < a.n_obs;
@@ -873,13 +774,6 @@ NJ_DEV void ode3_bwd_single(const KArgs& a, lfp lds_raw, int wave, int n_waves, 
     const unsigned long long tt1 = wall_clock64();
     t_pro += tt1 - tt0;
 #endif
-    // (the pop for the tile after this one: issued behind the prologue's loads -- vmcnt retires in
-    // order, in front of them the atomic's round trip sits on the chain order -> item -> record the
-    // first Euler step waits for: 9.0 instead of 5.4 us per tile -- and read at the tile's end.  The
-    // loop is written as `while (tile in range) { ...; tile = popped; }`: the first form, `for (;;) {
-    // tile = popped; if (out of range) break; ... }`, cost this kernel 72 spilled registers and 16
-    // scratch reloads per Euler step -- same live values, another loop shape for the allocator)
-    if constexpr (QUEUE) q_raw = queue_pop_issue(a.tile_q + 1);
     for (int s = nmax - 1; s >= 0; --s) {
       const float dt = s < it.n ? dt_r : 0.0f, t = t_r;
       const int sp = s > 0 ? s - 1 : 0;
@@ -991,26 +885,16 @@ NJ_DEV void ode3_bwd_single(const KArgs& a, lfp lds_raw, int wave, int n_waves, 
       float* dst = u < C::H ? out + u : trash;
       *dst = lam[q];
     }
-    if constexpr (QUEUE) {   // the tile after this one: popped when this one started
-#ifdef NJ_BWD_STAMPS
-      const unsigned long long tq0 = wall_clock64();
-#endif
-      q_rel = n_waves + queue_value(q_raw);
-#ifdef NJ_BWD_STAMPS
-      t_pop += wall_clock64() - tq0;
-#endif
-    }
   }
 
 #ifdef NJ_BWD_STAMPS
   BWD_STAMP(8, t_pro);
   BWD_STAMP(9, t_loop);
-  BWD_STAMP(10, t_pop);
 #endif
   BWD_STAMP(2, wall_clock64());
   BWD_STAMP(4, (unsigned long long)n_done);
   BWD_STAMP(5, (unsigned long long)n_steps_done);
-  (void)n_done; (void)n_steps_done; (void)q_rel;
+  (void)n_done; (void)n_steps_done;
   if (BWD_ABL(128)) return;
   ode3_flush<C, DROP>(a, lds_raw, G3, G2, GM, GN, G1, slab_row);
   BWD_STAMP(3, wall_clock64());

@@ -29,7 +29,7 @@ constexpr int PLAN_THREADS = 256;
 constexpr int PLAN_LDS_INTS = 4 * PLAN_KEYS + 96;
 constexpr int PLAN_SCAN_CHUNKS = 32;      // row blocks per key held in registers: 64 x 32 = 2 048
 constexpr int SPLIT_KMAX = 4095;
-struct SplitCfg { int on, ns[2], nw[2]; float r[2]; int queue[2]; };   // queue[v]: kernel v pops its tiles (tile queue)
+struct SplitCfg { int on, ns[2], nw[2]; float r[2]; };
 
 struct PlanJob {
   int P;                        // plan blocks in front of the launch (0: none)
@@ -264,19 +264,7 @@ __device__ inline void traj_layout_body(const int* len_hist, int n_obs, int K, l
       float cs = 0.0f, cw = 0.0f;
       if (t > 0) cs = sc.ns[v] > 0 ? fmaxf(l0, h / sc.ns[v]) / sc.r[v] : INF;
       if (t < n_tiles) cw = sc.nw[v] > 0 ? fmaxf(lt, (total - h) / sc.nw[v]) : INF;
-      float cost = fmaxf(cs, cw);
-      if (sc.queue[v] && sc.ns[v] > 0 && sc.nw[v] > 0) {
-        // Tile queue (njode_ode2.h): both roles pop until the tiles are gone -- four-wave blocks go
-        // on with the bulk's when theirs are done -- so the launch takes ~ mk = S / (nw + R ns)
-        // whatever T is; what T must guarantee is that no single tile outlasts that: the longest
-        // bulk tile (it starts first: the queue is longest-first) within 0.9 mk, the four-wave tiles
-        // within mk.  A tile costs a four-wave block 4 / R = ~2x the SIMD time it costs a bulk wave
-        // (profiles/r05_bwd_fixed_costs.txt: 2.3 us on four SIMDs against 4.6 us on one), so the
-        // SMALLEST such T is the cheapest.  (No T qualifies: the balance formula above.)
-        const float mk = total / ((float)sc.nw[v] + sc.r[v] * (float)sc.ns[v]);
-        const bool ok = lt <= 0.9f * mk && (t == 0 || (l0 / sc.r[v] <= mk && h / (sc.ns[v] * sc.r[v]) <= mk));
-        cost = ok ? (float)t * 1.0e-3f : 1.0e6f + cost;
-      }
+      const float cost = fmaxf(cs, cw);
       if (cost < bc[v]) { bc[v] = cost; bt[v] = t; }
     }
     h += lt;

@@ -16,9 +16,8 @@ namespace njode {
 // process by parse_env(), which states each one's values, default and effect (DESIGN.md section 4g
 // mirrors it)
 struct Env {
-  bool lock4, drop_bits_ahead, generic, ode_one_wave, sort_merge, sort_rocprim, item_pack, chain_delta, lock_sweep_valu, bwd_queue,
-      enc_fused, dw_enc_fused, tail_sort_rocprim, validate, plan_sort, plan_grid, plan_stamps, plan_stream,
-      plan_grid_tail;
+  bool lock4, drop_bits_ahead, generic, ode_one_wave, sort_merge, sort_rocprim, item_pack, chain_delta, lock_sweep_valu,
+      dw_enc_fused, tail_sort_rocprim, validate, plan_sort, plan_grid, plan_stamps, plan_stream, plan_grid_tail;
   int lock4_pt, chain_max, seg_chain_max, ode, split_bwd_blocks, split_fwd_blocks, bwd_blocks, fwd_blocks,
       plan_blocks, cs_shift, plan_inline_max, plan_inline_blocks, enc_blocks, chain_wpb;
   float split_r_bwd, split_r_fwd;
@@ -42,9 +41,9 @@ inline Env parse_env() {
   e.lock4_pt = num("NJODE_LOCK4_PT", 0);                // =1|2|4|8|16: paths per tile of the masked lockstep kernels (else: by batch size)
   e.chain_max = num("NJODE_CHAIN_MAX", 1 << 30);        // paths up to which the wave-per-path lockstep kernels run; 0: off (A/B)
   e.seg_chain_max = num("NJODE_SEG_CHAIN_MAX", 16384);  // waves up to which the wave-per-item segment kernels run; 0: off (A/B)
-  // implementation of the ODE-evolve kernels: valu | lds; mfma1 and anything else: the matrix cores, with
+  // implementation of the ODE-evolve kernels: valu; mfma1 and anything else: the matrix cores, with
   // mfma1 one wave per tile (njode_mfma.h) instead of the mixed kernels (A/B baseline)
-  e.ode = is(ode, "valu") ? ODE_VALU : is(ode, "lds") ? ODE_VALU_LDS : ODE_MFMA;
+  e.ode = is(ode, "valu") ? ODE_VALU : ODE_MFMA;
   e.ode_one_wave = is(ode, "mfma1");
   // =merge: rocPRIM's default dispatch instead of Onesweep (whose decoupled look-back spins between
   // workgroups and did not terminate under rocprofv3's FETCH_SIZE / WRITE_SIZE collection)
@@ -67,18 +66,8 @@ inline Env parse_env() {
   // -> 32: k_ode_bwd_mixed 0.436 -> 0.427 ms)
   e.split_bwd_blocks = num("NJODE_SPLIT_BWD_BLOCKS", 32);
   e.split_fwd_blocks = num("NJODE_SPLIT_FWD_BLOCKS", 96);
-  e.bwd_blocks = num("NJODE_BWD_BLOCKS", 0);            // all blocks of the backward (0: 1024, or two per CU with the queue)
+  e.bwd_blocks = num("NJODE_BWD_BLOCKS", 0);            // all blocks of the backward (0: 1024)
   e.fwd_blocks = num("NJODE_FWD_BLOCKS", 3072);
-  // (round 5) tile queue, =1: the launch is the resident blocks (two per CU), which pop their tiles,
-  // longest first, from a counter (njode_ode2.h).  Built, measured and NOT the default
-  // (profiles/r05_bwd_fixed_costs.txt): it removes the idle tail and buys 0.7 % at 20 000 paths, loses 5 %
-  // at 125 000 -- the Euler-step loop is bound by the SIMD's matrix / vector pipe, not by occupancy -- and
-  // it costs the bitwise reproducibility of the gradient (which tiles meet in an accumulator depends on
-  // timing).  Default: static snake rounds over 1024 blocks.
-  e.bwd_queue = on("NJODE_BWD_QUEUE");
-  // =1 (A/B, round 5): large plans of the segment plan -- the ODE forward's one-wave role
-  // evaluates the encoder at the head of every item (njode_ode2.h, ode2_item_start)
-  e.enc_fused = on("NJODE_ENC_FUSED");
   e.dw_enc_fused = not_off("NJODE_DW_ENC_FUSED");       // =0: the encoder's weight-gradient pass as a launch of its own (A/B)
   e.tail_sort_rocprim = is(getenv("NJODE_TAIL_SORT"), "rocprim");   // k_tail_keys + radix sort instead of k_tail_order
   e.plan_blocks = num("NJODE_PLAN_BLOCKS", 0);          // blocks of the one-launch plan (0: by row count)
@@ -186,7 +175,7 @@ inline Sizing size_call(const CfgOps& o, int B, int n_obs, int n_times, int K, i
             (double)B * steps * (2.0 * CHAIN_ACT_FLOATS * 4.0 + 16.0) <= rec_budget;
   z.delta_seg = z.delta && o.dims.width < 64;
   const int row_tiles = cdiv(n_obs + B, 16) + 128;
-  z.n_waves = std::max(4, (std::min(row_tiles, MAX_WAVES) + 3) & ~3);   // (whole 256-thread blocks: the LDS-weights variant)
+  z.n_waves = std::max(4, (std::min(row_tiles, MAX_WAVES) + 3) & ~3);   // (whole 256-thread blocks)
   // weight-gradient kernels of the lockstep backward: ~8 tiles of 16 (step, path) pairs per wave
   const long long w = ((long long)B * K / 16 + 7) / 8;
   z.n_waves_lock = ((int)std::min<long long>(1024, std::max<long long>(w, z.n_waves)) + 3) & ~3;
@@ -227,7 +216,6 @@ struct Route {
   int seg_ode;          // ODE-evolve implementation of the segment plan: `ode` where the shape has it
   int ode_split;        // the mixed ODE kernels (njode_mfma_split.h)
   int seg_chain;        // the wave-per-item ODE kernels (njode_chain_seg.h)
-  int enc_fused;        // the ODE forward's one-wave role evaluates the encoder
   int enc_blocks;       // grid cap of k_encode_rows_mfma
   bool tails_ride;      // the tails ride in the items' launch (k_seg_fwd_chain), else in one of their own
   // keep bits of the segment plan's ODE forward are drawn ahead, by spare blocks of the fragment-pack launch
@@ -235,7 +223,6 @@ struct Route {
   bool side, tails_side;   // the call has helper streams (route_side), and the tails run on the second one
   int defer_loss;       // 1: the loss is summed by the backward call (fused step), 2: rows in the forward call
   int dw_enc_fused;     // the encoder's weight-gradient pass rides in k_ode_dw_stored's launch
-  int tile_q_on;        // the mixed ODE backward pops its tiles from a queue
   int n_split_blocks, n_blocks_bwd, n_split_fwd, n_blocks_fwd;   // four-wave / all blocks of the mixed kernels
   int dw_pair_blocks, dw_seg_blocks;   // k_ode_dw_stored's roles
   bool chain_dw;        // the wave-per-chain sweeps' own weight-gradient kernel runs (njode_chain_dw.h)
@@ -253,9 +240,8 @@ inline int lock_kind(const CfgOps& o, const Sizing& z, const Env& e, bool mfma, 
   return LOCK_WAVE1;
 }
 
-// cus: compute units of the device (read only with NJODE_BWD_QUEUE=1)
 inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int K, int call_flags,
-                        const Env& e, bool tail, bool drop, bool want_hT, int cus) {
+                        const Env& e, bool tail, bool drop, bool want_hT) {
   Route r;
   r.size = z;
   r.drop = drop;
@@ -290,11 +276,10 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
                  : (call_flags & NJODE_C_LOSS_IN_BWD) ? 1 : (call_flags & NJODE_C_ROWS_IN_FWD) ? 2 : 0;
   // mixed ODE kernels: a plan with fewer tiles than resident blocks runs every tile four waves per tile
   const int n_tiles = cdiv(n_obs > 0 ? n_obs : 1, 16);
-  r.tile_q_on = (n_tiles > 384 && e.bwd_queue) ? 1 : 0;
   if (n_tiles <= 384) {
     r.n_split_blocks = r.n_blocks_bwd = n_tiles;
   } else {
-    const int tot_b = e.bwd_blocks > 0 ? e.bwd_blocks : (e.bwd_queue ? 2 * cus : 1024);
+    const int tot_b = e.bwd_blocks > 0 ? e.bwd_blocks : 1024;
     r.n_split_blocks = e.split_bwd_blocks;
     int nsb = tot_b - e.split_bwd_blocks;
     if (nsb > cdiv(n_tiles, 4)) nsb = cdiv(n_tiles, 4);
@@ -310,9 +295,6 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
     r.n_blocks_fwd = r.n_split_fwd + nsb;
   }
   r.seg_chain = (r.seg_mfma && r.ode_split && z.seg_items) ? 1 : 0;
-  // (the wave-per-item forward reads every row's encoder output: k_encode_rows_mfma)
-  r.enc_fused = (e.enc_fused && r.seg && r.ode == ODE_MFMA && r.ode_split && r.n_split_fwd < r.n_blocks_fwd &&
-                 !r.seg_chain) ? 1 : 0;
   r.enc_blocks = e.enc_blocks;
   r.tails_ride = r.tails && r.seg_chain;
   // (plans whose every tile runs four waves wide, i.e. small batches: there the forward IS the chain of its
@@ -333,7 +315,7 @@ inline Route route_call(const CfgOps& o, const Sizing& z, int B, int n_obs, int 
   r.chain_dw = (z.chain || r.seg_chain) && z.delta && z.delta_seg;
   r.dw_stored = r.chain_dw && r.dw_pair_blocks > 0;
   r.dw_enc_fused = (e.dw_enc_fused && r.seg_chain && r.dw_stored) ? 1 : 0;
-  r.hosts_plan = r.seg_mfma && r.ode_split && !r.enc_fused;
+  r.hosts_plan = r.seg_mfma && r.ode_split;
   r.needs_PT = !(r.lock_mfma || r.seg_mfma);
   return r;
 }

@@ -34,7 +34,7 @@ the readout of a path-output row):
 
   route (kernels)                                            ODE         ENC, DEC_BJ, DEC, ROW
   wave per item (k_seg_fwd_chain / k_seg_bwd_chain)          mc, Q1      mc, 16
-  split, mixed (k_ode_{fwd,bwd}_mixed, k_encode_rows_items)  mc, Q1      mc, 16
+  split, mixed (k_ode_{fwd,bwd}_mixed)                       mc, Q1      mc, 16
   one wave (k_ode_{fwd,bwd}_mfma, k_*_rows_mfma)             mc, Q1      mc, 16
   lockstep (k_paths_fwd_mfma, k_paths_bwd_adj_mfma)          mc, Q1      mc, 16
   four-wave lockstep (k_paths_fwd_mfma + lock4 backward)     mc, Q1      mc, 16

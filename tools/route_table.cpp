@@ -18,9 +18,9 @@ using namespace njode;
 #define ROUTE_FIELDS(X)                                                                                      \
   X(drop) X(want_path) X(want_loss) X(seg) X(tails) X(ode) X(seg_mfma) X(lock_sweep) X(lock_fwd)             \
   X(lock_fwd_kind) X(lock_bwd_kind) X(lock_bits_ahead) X(chain_wpb) X(lock_mfma) X(seg_ode) X(ode_split)     \
-  X(seg_chain) X(enc_fused) X(enc_blocks) X(tails_ride) X(seg_bits_ahead) X(defer_loss) X(dw_enc_fused)      \
-  X(tile_q_on) X(n_split_blocks) X(n_blocks_bwd) X(n_split_fwd) X(n_blocks_fwd) X(dw_pair_blocks)            \
-  X(dw_seg_blocks) X(chain_dw) X(dw_stored) X(hosts_plan) X(needs_PT)
+  X(seg_chain) X(enc_blocks) X(tails_ride) X(seg_bits_ahead) X(defer_loss) X(dw_enc_fused) X(n_split_blocks) \
+  X(n_blocks_bwd) X(n_split_fwd) X(n_blocks_fwd) X(dw_pair_blocks) X(dw_seg_blocks) X(chain_dw) X(dw_stored) \
+  X(hosts_plan) X(needs_PT)
 
 struct Size { int B, n_obs, K, n_times, budget; };   // budget: 0 default, 1 the activations fit but not the deltas, 2 nothing fits
 struct Inputs { int tail, drop, want_hT; };
@@ -29,7 +29,7 @@ static void print_call(int row, const CfgOps& o, const Size& s, int flags, const
   const double steps = s.K > 0 ? s.K : 1;
   const double budget = s.budget == 0 ? 16e9 : s.budget == 1 ? s.B * steps * (CHAIN_ACT_FLOATS * 4.0 + 16.0) : 1e3;
   const Sizing z = size_call(o, s.B, s.n_obs, s.n_times, s.K, flags, budget, env());
-  const Route r = route_call(o, z, s.B, s.n_obs, s.K, flags, env(), in.tail != 0, in.drop != 0, in.want_hT != 0, 256);
+  const Route r = route_call(o, z, s.B, s.n_obs, s.K, flags, env(), in.tail != 0, in.drop != 0, in.want_hT != 0);
   Route rs = r;
   route_side(rs, true);   // ... had build_plan taken helper streams
   const SlabRows w = slab_rows_written(r);

@@ -86,7 +86,6 @@ def main():
             'us_per_tile_step': round(float(sweep[m].sum() / max(steps[m].sum(), 1)), 3),
             'tile_prologue_us_per_tile': round(float(s[m, 8].sum() * tick / max(tiles[m].sum(), 1)), 3),
             'step_loop_us_per_step': round(float(s[m, 9].sum() * tick / max(steps[m].sum(), 1)), 3),
-            'queue_pop_us_per_tile': round(float(s[m, 10].sum() * tick / max(tiles[m].sum(), 1)), 3),
         }
         out[name] = d
         print('  ' + name)
