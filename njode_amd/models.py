@@ -20,6 +20,7 @@ What is different by construction:
   (no host sync); the default follows the reference harness, which calls
   ``.numpy()`` on them (``train.py:558,571,726``), and returns CPU tensors.
 """
+import copy
 import ctypes
 import os
 
@@ -190,7 +191,7 @@ class _Call:
     Dropping the last reference (e.g. an autograd graph that is never back-propagated)
     returns the workspace to the model's pool."""
     __slots__ = ('dims', 'batch', 'sched', 'flags', 'weight', 'p_drop', 'seed', 'ws',
-                 'keep', 'ws_slot', 'sched_obj', 'time_ptr')
+                 'keep', 'ws_slot', 'sched_obj', 'time_ptr', 'inputs', 'flat', 'stamp')
 
     def __del__(self):
         slot = getattr(self, 'ws_slot', None)
@@ -239,25 +240,48 @@ def _hT_and_loss_grads(model, call, grad_loss, grad_hT):
     return grad_flat
 
 
+def _check_saved(ctx, model, call):
+    """First statement of every backward: the forward's parameters and batch are still the ones it
+    ran on (``NJODE._stamp``), as plain autograd checks its saved tensors.  Host-side state only: the
+    parameters' version counters (``ctx.saved_tensors``), the flat vector's, the model's count of raw
+    writes, the batch tensors' version counters.  On a mismatch the workspace goes back to the pool
+    and nothing has been launched."""
+    try:
+        ctx.saved_tensors
+        if call.flat is not model._flat or call.stamp != model._stamp(call):
+            raise RuntimeError(
+                'one of the variables needed for gradient computation has been modified by an inplace '
+                'operation: the parameters (optimizer step, FusedAdam.step, a write to '
+                'flat_parameters(), .to()) or the batch tensors (X, start_X, M, obs_idx, n_obs_ot) of '
+                'this NJODE forward changed before its backward, which reads them again -- run the '
+                'forward again, or back-propagate before the change')
+    except RuntimeError:
+        model._release_ws(call)
+        raise
+
+
 class _NJODEFunction(torch.autograd.Function):
     """(loss, hT) = F(params); backward = exact discrete adjoint (njode_backward_f32); a gradient
     that reaches hT adds the pass of ``_hT_and_loss_grads``."""
 
     @staticmethod
-    def forward(ctx, model, call, loss, hT, *params):
+    def forward(ctx, model, call, outs, *params):
         ctx.model = model
         ctx.call = call
         ctx.set_materialize_grads(False)
-        # (views, not copies: `loss` and `hT` are this call's own fresh tensors; a clone was one more
-        # 5 us launch on the chain between the forward's last kernel and the backward's first)
-        return loss.view_as(loss), hT.view_as(hT)
+        ctx.save_for_backward(*params)
+        # (``outs`` = the call's own fresh (loss, hT), handed over inside a tuple: returned as they are,
+        # they are ordinary outputs of this node -- no copy, no launch, and no view of an input, on
+        # which ``loss += reg`` or ``hT += 1`` would raise)
+        return outs
 
     @staticmethod
     def backward(ctx, grad_loss, grad_hT):
         model, call = ctx.model, ctx.call
+        _check_saved(ctx, model, call)
         grad_flat = _hT_and_loss_grads(model, call, grad_loss, grad_hT)
         grads = [grad_flat[off:off + n].view(shape) for (off, n, shape) in model._param_slices]
-        return (None, None, None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 class _NJODEhTOnlyFunction(torch.autograd.Function):
@@ -266,15 +290,17 @@ class _NJODEhTOnlyFunction(torch.autograd.Function):
     step on the lockstep plan (``NJODE._grad_through_hT``)."""
 
     @staticmethod
-    def forward(ctx, model, call, hT, *params):
+    def forward(ctx, model, call, outs, *params):
         ctx.model = model
         ctx.call = call
         ctx.set_materialize_grads(False)
-        return hT.view_as(hT)
+        ctx.save_for_backward(*params)
+        return outs[0]
 
     @staticmethod
     def backward(ctx, grad_hT):
         model = ctx.model
+        _check_saved(ctx, model, ctx.call)
         if grad_hT is None:
             grad_flat = torch.zeros_like(model._flat)
         else:
@@ -377,6 +403,7 @@ class NJODE(torch.nn.Module):
         self._deferred_slots = []    # pinned schedule slots of plans whose launch is deferred
         self._deferred_plans = []    # ... and the plans themselves (their buffers stay alive until launched)
         self._last_hT_replay = None
+        self._param_writes = 0       # writes to the flat vector through its raw pointer (FusedAdam.step)
 
     # -- reference API ----------------------------------------------------------------
     def weight_decay_step(self):
@@ -390,6 +417,29 @@ class NJODE(torch.nn.Module):
         out = super()._apply(fn, *args, **kwargs)
         self._flat_checks = 63          # next _ensure_flat walks all parameters
         return out
+
+    # what belongs to ONE instance's calls: device buffers in use, pinned slots, queued plans, streams
+    _PER_INSTANCE = dict(_flat=None, _flat_checks=0, _flat_grad=None, _grad_bucket=None, _flat_present=None,
+                         _param_slices=None, _flat_params=None, _ones=None, _ring=None, _dims=None,
+                         _last_stream=None, _plan_stream=None, _deferred_stream=None, _last_hT_replay=None)
+    _PER_INSTANCE_LISTS = ('_ws_pool', '_plans', '_plan_pool', '_deferred_slots', '_deferred_plans')
+
+    def __deepcopy__(self, memo):
+        """``copy.deepcopy(model)``: parameters, buffers, gradients and settings are copied; the copy
+        starts with its own empty workspace pool, pinned ring, plan queue and schedule cache, and lays
+        its parameters out in a flat vector of its own on first use."""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k in self._PER_INSTANCE:
+                new.__dict__[k] = self._PER_INSTANCE[k]
+            elif k in self._PER_INSTANCE_LISTS:
+                new.__dict__[k] = []
+            elif k == '_sched_cache':
+                new.__dict__[k] = ScheduleCache()
+            else:
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
 
     # -- flat parameter storage -----------------------------------------------------------
     def _flat_slots(self):
@@ -551,6 +601,18 @@ class NJODE(torch.nn.Module):
             call.ws_slot[1] = False
             call.ws_slot = None
 
+    def _stamp(self, call):
+        """The host-side state of what a saved forward's backward reads again: the flat parameter
+        vector (its version counter; ``_param_writes`` for the writers that go through the raw
+        pointer) and the batch tensors the call kept (the caller's own tensors where they were
+        already fp32 / int32, contiguous and on the device; a copy otherwise, which nobody can
+        reach).  The parameters' own version counters are held by the autograd node."""
+        return (self._flat._version, self._param_writes) + tuple(t._version for t in call.inputs)
+
+    def _track(self, call):
+        call.flat = self._flat
+        call.stamp = self._stamp(call)
+
     def _make_call(self, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot,
                    return_path, get_loss, until_T, M, save_bwd, plan_key=None, plan_only=False,
                    want_hT=True, plan=None, rows_in_fwd=False, stream=None):
@@ -593,6 +655,7 @@ class NJODE(torch.nn.Module):
             n_d = n_obs_ot.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
             keep.append(n_d)
             n_ptr = n_d.data_ptr()
+        inputs = tuple(keep)
 
         slot_i, pinned = self._ring.acquire(sched.packed_nbytes())
         buf = pinned.numpy()
@@ -652,6 +715,7 @@ class NJODE(torch.nn.Module):
         call.ws_slot = self._acquire_ws(need.value, dev)
         call.ws = call.ws_slot[0]
         call.keep = keep + [pinned]
+        call.inputs = inputs
         call.sched_obj, call.time_ptr = sched, time_ptr      # (what _grad_through_hT re-packs)
         return call, sched, slot_i, B
 
@@ -896,8 +960,8 @@ class NJODE(torch.nn.Module):
         returns ``(hT, loss)`` or ``(hT, loss, path_t, path_h, path_y)``; ``loss`` is
         the Python int 0 when ``get_loss=False``.  ``plan`` (optional, not in the reference):
         the handle ``prefetch_plan`` returned for this batch."""
-        want_grad = (torch.is_grad_enabled() and get_loss
-                     and any(p.requires_grad for p in self.parameters()))
+        trainable = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = trainable and get_loss
         if self.torch_library_op and not return_path:
             return self._forward_via_op(times, time_ptr, X, obs_idx, delta_t, T, start_X,
                                         n_obs_ot, get_loss, until_T, M, want_grad)
@@ -905,6 +969,8 @@ class NJODE(torch.nn.Module):
             times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot, return_path,
             get_loss, until_T, M, save_bwd=want_grad,
             plan_key=(obs_idx, time_ptr), want_hT=True, plan=plan, rows_in_fwd=True)
+        if trainable:
+            self._track(call)
         dev = start_X.device
         hT = torch.empty(B, self.hidden_size, dtype=torch.float32, device=dev)
         loss = torch.zeros(1, dtype=torch.float32, device=dev) if get_loss else None
@@ -921,15 +987,14 @@ class NJODE(torch.nn.Module):
             raise
         if want_grad:
             self._ensure_flat()
-            loss_out, hT = _NJODEFunction.apply(self, call, loss, hT, *self._flat_params)
+            loss_out, hT = _NJODEFunction.apply(self, call, (loss, hT), *self._flat_params)
             loss_out = loss_out.reshape(())
         else:
             self._release_ws(call)
             loss_out = loss.reshape(()) if get_loss else 0
-            if (not get_loss and torch.is_grad_enabled()
-                    and any(p.requires_grad for p in self.parameters())):
+            if not get_loss and trainable:
                 self._ensure_flat()
-                hT = _NJODEhTOnlyFunction.apply(self, call, hT, *self._flat_params)
+                hT = _NJODEhTOnlyFunction.apply(self, call, (hT,), *self._flat_params)
         if get_loss and not self.device_outputs:
             loss_out = loss_out.cpu()       # reference harness calls .numpy() on it
         if return_path:
@@ -1090,6 +1155,9 @@ class FusedAdam:
             else:
                 torch.distributed.all_reduce(bucket, group=self.group)
         self.step_count += 1
+        # (the kernel writes through the raw pointer, past every version counter: a forward that was
+        # saved before this step must not be back-propagated after it, NJODE._stamp)
+        m._param_writes += 1
         _lib.check(_lib.lib().njode_adam_step_f32(
             flat.data_ptr(), grad.data_ptr(), self.exp_avg.data_ptr(),
             self.exp_avg_sq.data_ptr(), flat.numel(), self.lr, self.betas[0], self.betas[1],

@@ -63,6 +63,7 @@ def forward(params: List[Tensor], start_X: Tensor, X: Tensor, obs_idx: Tensor,
         raise
     cid = 0
     if save_bwd:
+        model._track(call)
         cid = _next_call[0]
         _next_call[0] += 1
         _CALLS[cid] = call
@@ -94,17 +95,19 @@ def _setup_context(ctx, inputs, output):
     ctx.n_params = len(inputs[0])
     ctx.call_id = int(output[2])
     ctx.set_materialize_grads(False)     # an unused output's gradient arrives as None, not zeros
+    ctx.save_for_backward(*inputs[0])    # (their version counters: models._check_saved)
     if ctx.call_id:
         weakref.finalize(ctx, _drop_call, ctx.call_id)
 
 
 def _backward(ctx, grad_hT, grad_loss, grad_id):
-    from .models import _hT_and_loss_grads
+    from .models import _check_saved, _hT_and_loss_grads
     model = _MODELS[ctx.model_id]
     call = _CALLS.pop(ctx.call_id, None)
     if call is None:
         raise RuntimeError('njode_amd::forward was not run with save_bwd=True, or its backward '
                            'already ran (a second backward is not supported)')
+    _check_saved(ctx, model, call)
     # (round 4 received grad_hT here and dropped it; now the hT term is differentiated too)
     grad_flat = _hT_and_loss_grads(model, call, grad_loss, grad_hT)
     grads = [grad_flat[off:off + n].view(shape) for (off, n, shape) in model._param_slices]
