@@ -37,6 +37,9 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
            # include/njode_protocol.h
            'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
+           # include/njode_records.h
+           'njode_records_bytes', 'njode_records_count', 'njode_records_fill',
+           'njode_records_heldout',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -101,6 +104,13 @@ class NjodeProtocolJob(C.Structure):
                 ('n_query', C.c_int32), ('rows', C.c_void_p), ('vals', C.c_void_p),
                 ('mask', C.c_void_p), ('X_val', C.c_void_p), ('M_val', C.c_void_p),
                 ('index_val', C.c_void_p)]
+
+
+class NjodeRecordStore(C.Structure):
+    _fields_ = [('n_records', C.c_int32), ('n_rows', C.c_int32), ('dim', C.c_int32),
+                ('n_grid', C.c_int32), ('drop_unobserved', C.c_int32), ('reserved', C.c_int32),
+                ('row_ptr', C.c_void_p), ('row_g', C.c_void_p), ('vals', C.c_void_p),
+                ('mask', C.c_void_p), ('att_min', C.c_void_p), ('att_max', C.c_void_p)]
 
 
 class NjodeError(RuntimeError):
@@ -184,11 +194,19 @@ def lib():
     L.njode_protocol_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
     L.njode_protocol_rows.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     L.njode_protocol_score_f32.argtypes = [C.POINTER(NjodeProtocolJob), vp, i32, vp, sz, vp]
+    L.njode_records_bytes.argtypes = [i32, i32, C.POINTER(sz)]
+    L.njode_records_count.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, vp, vp, vp, sz, vp]
+    L.njode_records_fill.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, vp, i32, i32, i32, vp,
+                                     vp, vp, vp, vp, sz, vp]
+    L.njode_records_heldout.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, vp, i32, i32, vp,
+                                        vp, vp, sz, vp]
     for name in ('njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
                  'njode_collate_count', 'njode_collate_fill',
                  'njode_cond_exp_bytes', 'njode_cond_exp_f64',
                  'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
                  'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
+                 'njode_records_bytes', 'njode_records_count', 'njode_records_fill',
+                 'njode_records_heldout',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
         getattr(L, name).restype = C.c_int

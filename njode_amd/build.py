@@ -139,6 +139,7 @@ def build(force=False, jobs=None, verbose=True):
     hdr_prod = os.path.join(os.path.dirname(HERE), 'include', 'njode_producer.h')
     hdr_self = os.path.join(os.path.dirname(HERE), 'include', 'njode_selftest.h')
     hdr_proto = os.path.join(os.path.dirname(HERE), 'include', 'njode_protocol.h')
+    hdr_rec = os.path.join(os.path.dirname(HERE), 'include', 'njode_records.h')
     kernel_deps = [os.path.join(CSRC, n) for n in
                    ('njode_cfg.hip', 'njode_host.h', 'njode_kernels.h', 'njode_device.h',
                     'njode_mfma.h', 'njode_mfma_rows.h', 'njode_lockstep_bwd.h',
@@ -160,6 +161,8 @@ def build(force=False, jobs=None, verbose=True):
         hdr, hdr_prod]
     proto_deps = [os.path.join(CSRC, n) for n in ('njode_protocol.hip', 'njode_error.h')] + [
         hdr, hdr_proto]
+    rec_deps = [os.path.join(CSRC, n) for n in ('njode_records.hip', 'njode_error.h')] + [
+        hdr, hdr_rec]
     tasks = []   # (object, command, digest)
     for i, (d, h, do, nh, w, act, masked, curt, res, rnn) in enumerate(cfgs):
         for part in range(6):
@@ -189,6 +192,12 @@ def build(force=False, jobs=None, verbose=True):
     proto_obj = os.path.join(OBJ, 'protocol.o')
     cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_protocol.hip'), '-o', proto_obj]
     tasks.append((proto_obj, cmd, _digest(proto_deps, ' '.join(cmd))))
+    # ... and the record collate (torch's fp32 (v - att_min) / att_max: one subtraction, one
+    # correctly rounded division)
+    rec_obj = os.path.join(OBJ, 'records.o')
+    cmd = common + ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
+                    os.path.join(CSRC, 'njode_records.hip'), '-o', rec_obj]
+    tasks.append((rec_obj, cmd, _digest(rec_deps, ' '.join(cmd))))
     if os.environ.get('NJODE_RESTAMP'):   # maintainer aid: adopt the objects on disk as current
         for t in tasks:
             if os.path.exists(t[0]):
@@ -203,7 +212,7 @@ def build(force=False, jobs=None, verbose=True):
     todo = [t for t in tasks if stale(t)]
     parts_only = os.environ.get('NJODE_PARTS_ONLY', '').strip()   # maintainer aid, e.g. "0": a change
     if parts_only:                                                 # that only touches those parts
-        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'protocol.o', 'gen.o')
+        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
                 with open(t[0] + '.stamp', 'w') as f:

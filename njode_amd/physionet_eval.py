@@ -121,17 +121,31 @@ def evaluate_model(model, batches, device, delta_t, T):
         return loss_val / count, mse_val / num_obs, mse_val_2 / count
 
 
-def _check_batch(model, b, delta_t, T):
+def _resident(a, shape, dev):
+    """Whether ``a`` is already what ``protocol.score`` takes: a contiguous fp32 tensor of
+    ``shape`` on ``dev`` (the device collate of ``records.RecordDataset`` builds such)."""
+    if not torch.is_tensor(a) or dev is None or a.device.type != dev.type:
+        return False
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return (a.device.index == index and a.dtype == torch.float32
+            and tuple(a.shape) == tuple(shape) and a.is_contiguous())
+
+
+def _check_batch(model, b, delta_t, T, dev=None):
     """What ``evaluate_model_device`` refuses about a batch before anything is launched: the
-    held-out arrays as fp32 numpy, the times as float64 and the ``path_t`` of the call."""
+    held-out arrays as fp32 numpy (or, when both are resident on ``dev`` already, as they are),
+    the times as float64 and the ``path_t`` of the call."""
     from . import protocol
     B, dim = int(b['batch_size']), int(b['X'].shape[1])
     times_val = np.asarray(b['times_val'], dtype=np.float64)
     if times_val.ndim != 1 or times_val.size == 0:
         raise ValueError('times_val must be a non-empty vector')
     shape = (B, len(times_val), dim)
-    vals = protocol.as_f32('vals_val', b['vals_val'], shape)
-    mask = protocol.as_f32('mask_val', b['mask_val'], shape)
+    if _resident(b['vals_val'], shape, dev) and _resident(b['mask_val'], shape, dev):
+        vals, mask = b['vals_val'], b['mask_val']
+    else:
+        vals = protocol.as_f32('vals_val', b['vals_val'], shape)
+        mask = protocol.as_f32('mask_val', b['mask_val'], shape)
     path_t = protocol.model_path_t(model, b['times'], delta_t, T)
     # the range check of get_comparison_times_ind
     assert np.min(path_t) < np.min(times_val) and np.max(path_t) + 1e-10 > np.max(times_val), \
@@ -147,7 +161,8 @@ def evaluate_model_device(model, batches, device, delta_t, T):
     errors are summed there in float64 (``protocol.score``; ``mse_val_2`` is taken in float64
     instead of fp32) and accumulate there over the batches together with the loss; the host
     reads four doubles and the loss once, after the last batch.  ``n_obs_ot`` is a device
-    ``bincount``, the held-out arrays are uploaded once per batch.  With
+    ``bincount``, the held-out arrays are uploaded once per batch -- unless both are contiguous fp32
+    tensors of the right shape on ``device`` already, which are used where they are.  With
     ``options['device_outputs']`` nothing in the loop waits for the device.
 
     Before anything is launched: the ``AssertionError`` of ``get_comparison_times_ind``'s range
@@ -156,7 +171,7 @@ def evaluate_model_device(model, batches, device, delta_t, T):
     observed, like the host arithmetic."""
     from . import protocol
     dev = protocol.need_cuda_device(device)
-    checked = [_check_batch(model, b, delta_t, T) for b in batches]
+    checked = [_check_batch(model, b, delta_t, T, dev) for b in batches]
     f64 = torch.float64
     with torch.no_grad():
         model.eval()
@@ -173,8 +188,9 @@ def evaluate_model_device(model, batches, device, delta_t, T):
                 until_T=True, return_path=True, get_loss=True, M=M)
             ind = protocol.rows(torch.from_numpy(np.asarray(path_t, dtype=np.float64)).to(dev),
                                 torch.from_numpy(times_val).to(dev), 'closest')
-            protocol.score(path_y, ind, vals=torch.from_numpy(vals).to(dev),
-                           mask=torch.from_numpy(mask).to(dev), out=acc[:4], accumulate=True)
+            if not torch.is_tensor(vals):
+                vals, mask = torch.from_numpy(vals).to(dev), torch.from_numpy(mask).to(dev)
+            protocol.score(path_y, ind, vals=vals, mask=mask, out=acc[:4], accumulate=True)
             acc[4] += e_loss.detach().to(device=dev, dtype=f64)
         sq_sum, num_obs, attr, _, loss_val = acc.cpu().tolist()
         count = len(batches)

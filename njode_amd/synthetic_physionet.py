@@ -19,6 +19,10 @@ to ``NJODE.forward`` through ``physionet_train.py:326-353``:
 Recipe: per path ``n_t ~ U{lo..hi}`` distinct grid
 times from a seeded ``RandomState``; per observation each feature is on with
 probability ``p_feature`` (at least one on); values ``U[0,1) * mask``.
+
+``make_records`` / ``make_climate_records`` build whole DATASETS in the raw form the reference's
+loaders hand to their collates -- a ragged list of ``(tt, vals, mask)`` -- for
+``records.RecordDataset``; ``make_batch`` is one ready-made batch with no dataset behind it.
 """
 import numpy as np
 import torch
@@ -86,3 +90,68 @@ def make_batch(batch_size=50, dim=PHYSIONET_DIM, n_grid=3000, n_obs_range=(30, 1
         'delta_t': 1.0 / n_grid if n_grid != 3000 else PHYSIONET_DELTA_T,
         'T': PHYSIONET_T,
     }
+
+
+def make_records(n_records=12, dim=PHYSIONET_DIM, n_quant=40, n_obs_range=(3, 10), p_feature=0.15,
+                 seed=0, zero_mask_rows=True):
+    """A synthetic record dataset in the raw form the reference's PhysioNet loader hands to its
+    collate (``physionet_LODE.py:428-544``): a list of ``(tt [T_i], vals [T_i, D], mask [T_i, D])``
+    fp32 arrays, and the per-feature ``data_min`` / ``data_max`` over the observed values
+    (``utils_LODE.get_data_min_max``).  Returns ``(records, data_min, data_max)``.
+
+    * times are hours on a quantisation grid, multiples of ``48 / n_quant`` in ``[0, 48]``, per
+      record ``T_i ~ U{lo..hi}`` distinct grid times; record 0 has its first row at t = 0;
+    * per row each feature is on with probability ``p_feature``; with ``zero_mask_rows`` about one
+      row in eight keeps an all-zero mask (the collate drops it: a union time without rows, a
+      record without any collated row), every other row has at least one feature on;
+    * values sit on a clinical-looking scale, ``50 j + 20 u`` for feature j, so that normalisation
+      is visible; they are 0 where the mask is 0, like the parsed PhysioNet files."""
+    rng = np.random.RandomState(seed)
+    lo, hi = n_obs_range
+    hi = min(hi, n_quant + 1)
+    lo = max(min(lo, hi), 1)
+    records = []
+    for n in range(n_records):
+        n_t = rng.randint(lo, hi + 1)
+        ks = np.sort(rng.choice(np.arange(n_quant + 1), size=n_t, replace=False))
+        if n == 0:
+            ks[0] = 0
+        mask = rng.random_sample((n_t, dim)) < p_feature
+        for r in range(n_t):
+            if zero_mask_rows and rng.random_sample() < 0.125:
+                mask[r] = False
+            elif not mask[r].any():
+                mask[r, rng.randint(dim)] = True
+        if zero_mask_rows and n == 1:
+            mask[:] = False            # a record none of whose rows is collated
+        vals = (50.0 * np.arange(dim)[None, :] + 20.0 * rng.random_sample((n_t, dim))) * mask
+        # (hours in float64, rounded to fp32 once: the last grid time is 48 exactly)
+        records.append(((ks * 48.0 / n_quant).astype(np.float32), vals.astype(np.float32),
+                        mask.astype(np.float32)))
+    all_v = np.concatenate([r[1] for r in records])
+    all_m = np.concatenate([r[2] for r in records]) > 0
+    data_min = np.where(all_m.any(0), np.where(all_m, all_v, np.inf).min(0), 0).astype(np.float32)
+    data_max = np.where(all_m.any(0), np.where(all_m, all_v, -np.inf).max(0), 0).astype(np.float32)
+    return records, data_min, data_max
+
+
+def make_climate_records(n_records=12, dim=5, n_obs_range=(3, 10), p_feature=0.5, seed=0):
+    """Records shaped like the climate data of ``GRU_ODE_Bayes/data_utils_gru_ode_bayes.py``
+    (``ODE_Dataset`` rows ``ID, Time, Value_*, Mask_*``): few features, float times in ``[0, 200]``
+    with one decimal, every row with at least one feature on, values left as they are (also where
+    the mask is 0).  For ``RecordDataset.from_records(..., time_div=None, drop_unobserved=False)``
+    without normalisation.  Returns the list of ``(tt, vals, mask)`` fp32 arrays."""
+    rng = np.random.RandomState(seed)
+    lo, hi = n_obs_range
+    records = []
+    for n in range(n_records):
+        n_t = rng.randint(lo, hi + 1)
+        ks = np.sort(rng.choice(np.arange(2001), size=n_t, replace=False))
+        mask = rng.random_sample((n_t, dim)) < p_feature
+        for r in range(n_t):
+            if not mask[r].any():
+                mask[r, rng.randint(dim)] = True
+        vals = rng.standard_normal((n_t, dim))
+        records.append(((ks / 10.0).astype(np.float32), vals.astype(np.float32),
+                        mask.astype(np.float32)))
+    return records

@@ -1,0 +1,191 @@
+"""
+Training / evaluation loop of the masked NJ-ODE model on a dataset of irregular records.
+
+Reproduces the compute semantics of the reference harness ``NJODE/physionet_train.py:259-392``
+-- nothing of its experiment management (model-id registry, parser, Telegram) -- on a
+``records.RecordDataset``:
+
+* model with ``options['masked'] = True``, ``Adam(lr, weight_decay=0.0005)`` (``:152, 259-269``);
+* per optimizer step (``:328-353``): the train-layout collate of the batch, ``n_obs_ot`` counted
+  from ``obs_idx``, ``start_X = 0``, ``model(..., M=M)`` in train mode, backward, step;
+* per epoch (``:356-392``): ``evaluate_model`` on the test-layout batches of the test records
+  (observe the first half of each batch's time axis, score the second half), ``train_loss`` =
+  the last batch's loss, one metric row of ``METR_COLUMNS``, ``best_checkpoint`` on a lower
+  ``eval_metric``, ``last_checkpoint`` + metric file every ``save_every`` epochs,
+  ``model.epoch += 1``, ``model.weight_decay_step()``;
+* ``resume_training`` / ``load_best`` (``:274-292``) continue from those checkpoints.
+
+Batches follow ``parallel.epoch_permutation`` like ``train.train``.  The fused step
+(``NJODE.loss_and_grad`` + ``FusedAdam``) is the default; ``fused=False`` drives the model like
+the reference (``loss.backward()`` + ``torch.optim.Adam``).  Single process only.
+"""
+import csv
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import models, parallel, physionet_eval, synthetic_physionet
+
+METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss', 'eval_metric',
+                'eval_metric_2']
+NN = ((50, 'tanh'), (50, 'tanh'))
+
+
+def _upload(b, device):
+    """A ``collate_host`` batch with the tensors of the step on the device (held-out arrays stay
+    numpy: ``evaluate_model_device`` uploads them per call)."""
+    d = dict(b)
+    for k in ('X', 'M', 'start_X'):
+        d[k] = b[k].to(device)
+    d['obs_idx'] = b['obs_idx'].to(device, torch.int32)
+    d['n_obs_ot'] = b['n_obs_ot'].to(device, torch.int32)
+    return d
+
+
+def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learning_rate=1e-3,
+                  hidden_size=41, bias=True, dropout_rate=0.1, ode_nn=NN, readout_nn=NN, enc_nn=NN,
+                  use_rnn=False, solver='euler', weight=0.5, weight_decay=1.,
+                  delta_t=synthetic_physionet.PHYSIONET_DELTA_T, T=synthetic_physionet.PHYSIONET_T,
+                  device='cuda', fused=True, device_collate=True, shuffle_seed=0, log=print,
+                  model_path=None, model_id=1, save_every=1, resume_training=False,
+                  load_best=False, plan_ahead=True, init_state=None, **options):
+    """Train on the records ``train_idx`` of ``dataset`` (a ``records.RecordDataset``), evaluate on
+    ``test_idx`` after every epoch.  Returns ``(model, metrics)`` with one row of ``METR_COLUMNS``
+    per epoch.
+
+    ``device_collate=True`` builds every batch with the GPU collate of the resident store -- phase
+    1 for a whole epoch at once (one upload, one copy back, one wait), phase 2 one batch ahead,
+    and the next batch's execution plan prefetched beside the current step under the conditions
+    ``train.train`` applies; the test batches, held-out arrays included, are built once and stay in
+    HBM.  ``device_collate=False`` collates on the host (``collate_host``) and uploads: the same
+    batches, bit for bit.  ``ValueError`` under a process group of more than one rank."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() \
+            and torch.distributed.get_world_size() > 1:
+        raise ValueError('train_records is single process: multi-GPU record training is not offered')
+    train_idx = np.asarray(train_idx, dtype=np.int64).reshape(-1)
+    test_idx = np.asarray(test_idx, dtype=np.int64).reshape(-1)
+    if len(train_idx) == 0 or len(test_idx) == 0 or batch_size <= 0:
+        raise ValueError('train_idx, test_idx and batch_size must not be empty')
+    if device_collate and dataset.device is None:
+        raise ValueError('device_collate needs a RecordDataset resident on the GPU')
+    dev = torch.device(device)
+    model_opts = dict(options)
+    model_opts['masked'] = True
+    model_opts['device_outputs'] = True
+    dim = dataset.dim
+    torch.manual_seed(0)
+    model = models.NJODE(dim, hidden_size, dim, ode_nn, readout_nn, enc_nn, use_rnn, bias=bias,
+                         dropout_rate=dropout_rate, solver=solver, weight=weight,
+                         weight_decay=weight_decay, options=model_opts).to(dev)
+    if init_state is not None:
+        model.load_state_dict(init_state)
+    if fused:
+        optimizer = models.FusedAdam(model, lr=learning_rate, weight_decay=0.0005)
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate, weight_decay=0.0005)
+
+    # the test batches never change: collated once, in the records' order
+    test_lists = [test_idx[i:i + batch_size] for i in range(0, len(test_idx), batch_size)]
+    if device_collate:
+        test_batches = [dataset.fill_batch(p) for p in dataset.prepare_batches(test_lists, 'test')]
+    else:
+        test_batches = [_upload(dataset.collate_host(ix, 'test'), dev) for ix in test_lists]
+
+    best_eval_metric = np.inf
+    path_last = path_best = metric_file = None
+    saved_rows = []
+    if model_path is not None:
+        model_dir = os.path.join(model_path, 'id-{}'.format(model_id))
+        path_last = os.path.join(model_dir, 'last_checkpoint')
+        path_best = os.path.join(model_dir, 'best_checkpoint')
+        metric_file = os.path.join(model_dir, 'metric_id-{}.csv'.format(model_id))
+        os.makedirs(model_dir, exist_ok=True)
+        if resume_training and os.path.exists(os.path.join(
+                path_best if load_best else path_last, 'checkpt.tar')):
+            models.get_ckpt_model(path_best if load_best else path_last, model, optimizer, dev)
+            if os.path.exists(metric_file):
+                with open(metric_file) as f:
+                    saved_rows = [[float(x) for x in r[1:]] for r in list(csv.reader(f))[1:]]
+                if saved_rows:
+                    best_eval_metric = min(r[5] for r in saved_rows)
+            model.epoch += 1
+            model.weight_decay_step()
+
+    def write_metrics():
+        # pandas' DataFrame.to_csv layout: unnamed index column first
+        with open(metric_file, 'w', newline='') as f:
+            wr = csv.writer(f)
+            wr.writerow([''] + METR_COLUMNS)
+            for i, r in enumerate(saved_rows):
+                wr.writerow([i] + r)
+
+    def plan_epoch(epoch):
+        order = train_idx[parallel.epoch_permutation(len(train_idx), epoch, shuffle_seed)]
+        lists = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+        return lists, dataset.prepare_batches(lists, 'train') if device_collate else None
+
+    plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
+    metrics, pending, epoch_plan = [], [], {}
+    while model.epoch <= epochs:
+        t0 = time.time()
+        model.train()
+        lists, prepared = epoch_plan.pop(model.epoch, None) or plan_epoch(model.epoch)
+
+        def prepare(s):
+            if device_collate:
+                return dataset.fill_batch(prepared[s])
+            return _upload(dataset.collate_host(lists[s], 'train'), dev)
+
+        loss = None
+        nxt = prepare(0)
+        for s in range(len(lists)):
+            d = nxt
+            nxt = prepare(s + 1) if s + 1 < len(lists) else None
+            # (the conditions of train.train; a masked model never defers its plan)
+            if plan_ahead and fused and nxt is not None and \
+                    (nxt['batch_size'] <= 512 or nxt['batch_size'] >= 4096):
+                model.prefetch_plan(nxt['times'], nxt['time_ptr'], nxt['X'], nxt['obs_idx'], delta_t,
+                                    T, nxt['start_X'], nxt['n_obs_ot'], M=nxt['M'], need_hT=True)
+            args = (d['times'], d['time_ptr'], d['X'], d['obs_idx'], delta_t, T, d['start_X'],
+                    d['n_obs_ot'])
+            optimizer.zero_grad()
+            if fused:
+                _, loss = model.loss_and_grad(*args, M=d['M'])
+            else:
+                _, loss = model(*args, return_path=False, get_loss=True, M=d['M'])
+                loss.backward()
+            optimizer.step()
+        # the next epoch's order and collate counts, queued behind this epoch's steps: their one
+        # host wait is the end-of-epoch wait the loop needs anyway
+        if device_collate and model.epoch + 1 <= epochs:
+            epoch_plan[model.epoch + 1] = plan_epoch(model.epoch + 1)
+        torch.cuda.synchronize(dev)
+        train_time = time.time() - t0
+
+        t0 = time.time()
+        loss_val, mse_val, mse_val_2 = physionet_eval.evaluate_model_device(
+            model, test_batches, dev, delta_t, T)
+        eval_time = time.time() - t0
+        train_loss = float(loss.detach())
+        log("epoch {}, weight={:.5f}, train-loss={:.5f}, eval-loss={:.5f}, eval-metric={:.5f}, "
+            "eval-metric_2={:.5f}".format(model.epoch, model.weight, train_loss, loss_val, mse_val,
+                                          mse_val_2))
+        row = [model.epoch, train_time, eval_time, train_loss, loss_val, mse_val, mse_val_2]
+        metrics.append(row)
+        pending.append(row)
+        if model_path is not None:
+            if mse_val < best_eval_metric:
+                log('save new best model: last-best-metric: {:.5f}, new-best-metric: {:.5f}, '
+                    'epoch: {}'.format(best_eval_metric, mse_val, model.epoch))
+                models.save_checkpoint(model, optimizer, path_best, model.epoch)
+                best_eval_metric = mse_val
+            if model.epoch % save_every == 0:
+                saved_rows.extend(pending)
+                pending = []
+                write_metrics()
+                models.save_checkpoint(model, optimizer, path_last, model.epoch)
+        model.epoch += 1
+        model.weight_decay_step()
+    return model, metrics
