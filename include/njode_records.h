@@ -13,6 +13,10 @@
  *                                 NJODE/physionet_train.py:336-340 recounts it from obs_idx
  *   njode_records_heldout         physionet_LODE.py:489-496 (data_type == "test": the dense
  *                                 second half of the batch's time axis)
+ *   njode_records_val_count /     data_utils_gru_ode_bayes.py:160-183 (ODE_Dataset, validation:
+ *   _val_fill                     df_before / df_after, groupby("ID").head(max_val_samples)) and
+ *                                 :257-265 (custom_collate_fn: X_val, M_val, times_val,
+ *                                 index_val sorted by ID, then Time)
  *
  * Conventions are those of njode_hip.h (device pointers, caller-owned buffers, caller's stream,
  * int return code + njode_last_error()).  Nothing is allocated, nothing is kept between calls:
@@ -90,6 +94,46 @@ int njode_records_heldout(const NjodeRecordStore* store, const int32_t* batch_id
  * only one of att_min / att_max, a range that is not 0 <= g_lo <= g_hi <= G, a negative n_obs
  * or n_val; NJODE_E_WORKSPACE for a null or too small workspace -- before anything is
  * launched. */
+
+/* ---- the climate validation layout ------------------------------------------------------------
+ * ODE_Dataset(validation=True, val_options={T_val, max_val_samples}) + custom_collate_fn: the rows
+ * up to the cut are observed, of the rows after it each record gives its first max_val, and
+ * these are listed by (record index, time) with the batch position of their record beside them.
+ * The cut is a grid index: g_cut = number of grid points <= float32(T_val) (the reference compares
+ * the fp32 Time column); a row is observed if row_g < g_cut and held out otherwise.  The observed
+ * part is njode_records_count / _fill with g_hi = g_cut; the two calls below build the held-out
+ * part.  They take a store with drop_unobserved = 0 only: the layout belongs to the collate that
+ * keeps every row. */
+
+/* workspace of one call of either entry point below, in bytes: int32 [2][B] (held-out rows and
+ * first held-out row of every batch position) */
+int njode_records_val_bytes(int32_t B, size_t* out);
+
+/* Held-out part, phase 1.  Every batch position finds its first row with row_g >= g_cut (binary
+ * search) and holds min(max_val, rows left) rows.  val_ptr: device int32 [B + 1]; val_ptr[b] =
+ * offset of position b's rows in the output order, which is by record index (the value of
+ * batch_idx[b], compared as an int32), positions that hold the same record by batch position,
+ * then time; val_ptr[B] = L, the number of held-out rows, which the caller copies to the host to
+ * size the outputs.  An index outside [0, N) counts as a record without rows.  The order is an
+ * exact count over all pairs of positions, in integers: any B, the same bits every time. */
+int njode_records_val_count(const NjodeRecordStore* store, const int32_t* batch_idx, int32_t B,
+                            int32_t g_cut, int32_t max_val, int32_t* val_ptr, void* ws,
+                            size_t ws_bytes, njodeStream_t stream);
+
+/* Held-out part, phase 2, with val_ptr as written by phase 1 (device) and L = val_ptr[B]:
+ * X_val, M_val fp32 [L][D] (values as in X), g_val int32 [L] (grid index of the row's time:
+ * times_val = grid[g_val]), index_val int32 [L] (batch position of the row's record).  Every
+ * cell of the four outputs is written; L bounds every row written; the outputs may be NULL when
+ * L is 0. */
+int njode_records_val_fill(const NjodeRecordStore* store, const int32_t* batch_idx, int32_t B,
+                           int32_t g_cut, int32_t max_val, const int32_t* val_ptr, int32_t L,
+                           float* X_val, float* M_val, int32_t* g_val, int32_t* index_val,
+                           void* ws, size_t ws_bytes, njodeStream_t stream);
+
+/* Both: NJODE_E_BADARG for a null store, array, batch_idx, val_ptr or output, N, R, D, G, B or
+ * max_val not positive, only one of att_min / att_max, a store with drop_unobserved = 1, g_cut
+ * outside [0, G], B * min(max_val, R) beyond 31 bits, a negative L; NJODE_E_WORKSPACE for a null
+ * or too small workspace -- before anything is launched. */
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,8 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
            # include/njode_records.h
            'njode_records_bytes', 'njode_records_count', 'njode_records_fill',
-           'njode_records_heldout',
+           'njode_records_heldout', 'njode_records_val_bytes', 'njode_records_val_count',
+           'njode_records_val_fill',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -200,13 +201,19 @@ def lib():
                                      vp, vp, vp, vp, sz, vp]
     L.njode_records_heldout.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, vp, i32, i32, vp,
                                         vp, vp, sz, vp]
+    L.njode_records_val_bytes.argtypes = [i32, C.POINTER(sz)]
+    L.njode_records_val_count.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, i32, i32, vp, vp,
+                                          sz, vp]
+    L.njode_records_val_fill.argtypes = [C.POINTER(NjodeRecordStore), vp, i32, i32, i32, vp, i32,
+                                         vp, vp, vp, vp, vp, sz, vp]
     for name in ('njode_philox4x32_10', 'njode_generate_paths', 'njode_sample_observations',
                  'njode_collate_count', 'njode_collate_fill',
                  'njode_cond_exp_bytes', 'njode_cond_exp_f64',
                  'njode_generate_stage', 'njode_cond_exp_staged_bytes', 'njode_cond_exp_staged_f64',
                  'njode_protocol_bytes', 'njode_protocol_rows', 'njode_protocol_score_f32',
                  'njode_records_bytes', 'njode_records_count', 'njode_records_fill',
-                 'njode_records_heldout',
+                 'njode_records_heldout', 'njode_records_val_bytes', 'njode_records_val_count',
+           'njode_records_val_fill',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
         getattr(L, name).restype = C.c_int

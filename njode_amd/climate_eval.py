@@ -121,12 +121,34 @@ def evaluate_model(model, batches, device, delta_t, T):
         return loss_val / len(batches), mse_val / num_obs
 
 
-def _check_batch(b):
+def _resident(a, shape, dtype, dev):
+    """Whether ``a`` is already what the protocol kernels take: a contiguous tensor of ``shape`` and
+    ``dtype`` on ``dev`` (``records.RecordDataset.collate_val`` builds such) -- the rule of
+    ``physionet_eval._resident``."""
+    if not torch.is_tensor(a) or a.device.type != dev.type:
+        return False
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return (a.device.index == index and a.dtype == dtype and tuple(a.shape) == tuple(shape)
+            and a.is_contiguous())
+
+
+def _check_batch(b, dev=None):
     """What ``evaluate_model_device`` refuses about a batch before anything is launched: the
-    held-out arrays as fp32 numpy, the times as float64, ``index_val`` as int32."""
+    held-out arrays as fp32 numpy, the times as float64, ``index_val`` as int32 -- or, when all
+    four are resident on ``dev`` in those types already, as they are (their ``index_val`` is the
+    collate kernels' and is not read back)."""
     from . import protocol
     B, dim = len(b['pat_idx']), int(b['X'].shape[1])
-    times_val = np.asarray(b['times_val'], dtype=np.float64)
+    if dev is not None and torch.is_tensor(b['times_val']) and b['times_val'].dim() == 1:
+        L = b['times_val'].shape[0]
+        if _resident(b['times_val'], (L,), torch.float64, dev) \
+                and _resident(b['X_val'], (L, dim), torch.float32, dev) \
+                and _resident(b['M_val'], (L, dim), torch.float32, dev) \
+                and _resident(b['index_val'], (L,), torch.int32, dev):
+            return b['X_val'], b['M_val'], b['times_val'], b['index_val']
+    times_val = b['times_val']
+    times_val = np.asarray(times_val.detach().cpu() if torch.is_tensor(times_val) else times_val,
+                           dtype=np.float64)
     if times_val.ndim != 1:
         raise ValueError('times_val must be a vector')
     L = len(times_val)
@@ -153,13 +175,19 @@ def evaluate_model_device(model, batches, device, delta_t, T):
     the host reads four doubles and the loss once, after the last batch.  With
     ``options['device_outputs']`` nothing in the loop waits for the device.
 
+    A batch whose ``X_val``, ``M_val`` (fp32 ``[L, dim]``), ``index_val`` (int32 ``[L]``) and
+    ``times_val`` (float64 ``[L]``) are contiguous tensors on ``device`` already -- the device
+    collate of ``records.RecordDataset`` -- is scored where it lies: nothing is copied to the host
+    or back, and an ``n_obs_ot`` tensor on the device is used instead of a recount of ``obs_idx``.
+
     ``ValueError``, before anything is launched: an ``index_val`` outside ``[0, B)`` or not of an
     integer type, held-out arrays whose shapes disagree with the batch or each other, a ``device``
     that is not a GPU.  ``ZeroDivisionError`` if no held-out entry was observed, like the host
     arithmetic."""
     from . import protocol
     dev = protocol.need_cuda_device(device)
-    checked = [_check_batch(b) for b in batches]
+    checked = [_check_batch(b, dev) for b in batches]
+    up = lambda a: a if torch.is_tensor(a) else torch.from_numpy(a).to(dev)  # noqa: E731
     f64 = torch.float64
     with torch.no_grad():
         model.eval()
@@ -169,18 +197,19 @@ def evaluate_model_device(model, batches, device, delta_t, T):
             X = b['X'].to(dev)
             M = b['M'].to(dev)
             obs_idx = b['obs_idx'].to(dev)
-            n_obs_ot = torch.bincount(obs_idx, minlength=b_size)
+            n_obs_ot = b.get('n_obs_ot')
+            if not (torch.is_tensor(n_obs_ot) and n_obs_ot.device == X.device
+                    and tuple(n_obs_ot.shape) == (b_size,)):
+                n_obs_ot = torch.bincount(obs_idx, minlength=b_size)
             start_X = torch.zeros(b_size, X.shape[1], dtype=torch.float32, device=dev)
             _, e_loss, path_t, _, path_y = model(
                 b['times'], b['time_ptr'], X, obs_idx, delta_t, T, start_X, n_obs_ot,
                 until_T=True, return_path=True, get_loss=True, M=M)
             # round the floating point error out of the time vector (reference :549-551)
             t_vec = np.around(path_t, n_decimals(delta_t)).astype(np.float32).astype(np.float64)
-            ind = protocol.rows(torch.from_numpy(t_vec).to(dev), torch.from_numpy(times_val).to(dev),
-                                'first_nearest')
-            protocol.score(path_y, ind, X_val=torch.from_numpy(X_val).to(dev),
-                           M_val=torch.from_numpy(M_val).to(dev),
-                           index_val=torch.from_numpy(index_val).to(dev), out=acc[:4], accumulate=True)
+            ind = protocol.rows(torch.from_numpy(t_vec).to(dev), up(times_val), 'first_nearest')
+            protocol.score(path_y, ind, X_val=up(X_val), M_val=up(M_val), index_val=up(index_val),
+                           out=acc[:4], accumulate=True)
             acc[4] += e_loss.detach().to(device=dev, dtype=f64)
         sq_sum, num_obs, _, _, loss_val = acc.cpu().tolist()
         return loss_val / len(batches), sq_sum / num_obs

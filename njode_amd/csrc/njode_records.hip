@@ -8,6 +8,10 @@
 // index scans its B cells: counts them (phase 1), ranks them with the ballot scan of
 // k_collate_fill (njode_producer.hip) and writes their rows (phase 2), or spreads them over the
 // dense held-out arrays (phase 2b).  Byte / fp32 streaming work, no matrix cores, no atomics.
+//
+// The climate validation layout (njode_records_val_*) needs no table for its held-out part: a
+// record's rows after the cut are contiguous in the store, so a binary search per batch position,
+// an exact rank of the positions by (record, position) and a contiguous copy per position do it.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -207,6 +211,127 @@ __global__ void __launch_bounds__(CB) k_records_heldout(NjodeRecordStore s, int 
   }
 }
 
+// ---- the climate validation layout: the rows after the cut, by (record, batch position, time) ----
+// Workspace of the three kernels below: int32 [2][B], n_val[b] then first[b] (row of the store).
+
+// thread b: a binary search in its record's strictly increasing row_g for the first row with
+// row_g >= g_cut; it holds min(max_val, rows left) held-out rows.  31 halvings cover any range.
+__global__ void __launch_bounds__(CB) k_records_val_search(NjodeRecordStore s,
+                                                           const int* __restrict__ idx, int B,
+                                                           int g_cut, int max_val,
+                                                           int* __restrict__ n_val,
+                                                           int* __restrict__ first) {
+  const int b = blockIdx.x * CB + threadIdx.x;
+  if (b >= B) return;
+  const int n = idx[b];
+  int r0 = 0, r1 = 0;
+  if (n >= 0 && n < s.n_records) {
+    r0 = min(max(s.row_ptr[n], 0), s.n_rows);
+    r1 = max(min(s.row_ptr[n + 1], s.n_rows), r0);
+  }
+  int lo = r0, hi = r1;   // first row >= g_cut lies in [lo, hi]
+  for (int it = 0; it < 31; ++it) {
+    if (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (s.row_g[mid] < g_cut) lo = mid + 1; else hi = mid;
+    }
+  }
+  n_val[b] = min(max_val, r1 - lo);
+  first[b] = lo;
+}
+
+// thread b: val_ptr[b] = held-out rows of the batch positions that come before b in the order
+// (record index, batch position) -- an exact count over all positions, staged through LDS in
+// tiles of CB; integers only, so any B gives the same bits.  val_ptr[B] = all of them.
+__global__ void __launch_bounds__(CB) k_records_val_rank(const int* __restrict__ idx, int B,
+                                                         const int* __restrict__ n_val,
+                                                         int* __restrict__ val_ptr) {
+  __shared__ int sh_key[CB];
+  __shared__ int sh_n[CB];
+  const int b = blockIdx.x * CB + threadIdx.x;
+  const int key = b < B ? idx[b] : 0;
+  int before = 0, total = 0;
+  for (int b0 = 0; b0 < B; b0 += CB) {   // (block-uniform bounds: the barriers are safe)
+    const int o = b0 + threadIdx.x;
+    __syncthreads();
+    sh_key[threadIdx.x] = o < B ? idx[o] : 0;
+    sh_n[threadIdx.x] = o < B ? n_val[o] : 0;
+    __syncthreads();
+    const int m = min(CB, B - b0);
+    for (int i = 0; i < m; ++i) {
+      const int k = sh_key[i], c = sh_n[i];
+      total += c;
+      before += (k < key || (k == key && b0 + i < b)) ? c : 0;
+    }
+  }
+  if (b < B) val_ptr[b] = before;
+  if (b == B - 1) val_ptr[B] = total;
+}
+
+// wave w of the launch = batch position b: its n_val[b] held-out rows are contiguous in the store
+// (first[b] ...) and contiguous in the outputs (val_ptr[b] ...), so the wave copies n_val * D
+// elements with unit stride on both sides.  L bounds every row written.
+__global__ void __launch_bounds__(CB) k_records_val_fill(NjodeRecordStore s, int B,
+                                                         const int* __restrict__ n_val,
+                                                         const int* __restrict__ first,
+                                                         const int* __restrict__ val_ptr, int L,
+                                                         float* __restrict__ X_val,
+                                                         float* __restrict__ M_val,
+                                                         int* __restrict__ g_val,
+                                                         int* __restrict__ index_val) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (CB / 64) + (threadIdx.x >> 6);
+  if (b >= B) return;   // wave-uniform
+  const int n = n_val[b], r0 = first[b], base = val_ptr[b];
+  const int D = s.dim;
+  if (n <= 0 || r0 < 0 || n > s.n_rows - r0) return;   // (rebuilt by this call: cannot happen)
+  for (int q = lane; q < n; q += 64) {
+    const int out = base + q;
+    if ((unsigned)out >= (unsigned)L) continue;
+    g_val[out] = s.row_g[r0 + q];
+    index_val[out] = b;
+  }
+  const long long cells = (long long)n * D;
+  for (long long e = lane; e < cells; e += 64) {
+    const int q = (int)(e / D), j = (int)(e - (long long)q * D);
+    const int out = base + q;
+    if ((unsigned)out >= (unsigned)L) continue;
+    const size_t src = (size_t)(r0 + q) * D + j;
+    const uint8_t mk = s.mask[src];
+    X_val[(size_t)out * D + j] = norm_value(s.vals[src], mk, s.att_min, s.att_max, j);
+    M_val[(size_t)out * D + j] = mk ? 1.0f : 0.0f;
+  }
+}
+
+size_t val_ws_bytes(int B) { return 2 * (size_t)B * sizeof(int32_t); }
+
+// what the two validation entry points refuse about the store, the batch and the workspace
+int check_val_call(const NjodeRecordStore* s, const int32_t* batch_idx, int32_t B, int32_t g_cut,
+                   int32_t max_val, const int32_t* val_ptr, const void* ws, size_t ws_bytes) {
+  if (!s) return fail(NJODE_E_BADARG, "null store");
+  if (s->n_records <= 0 || s->n_rows <= 0 || s->dim <= 0 || s->n_grid <= 0)
+    return fail(NJODE_E_BADARG, "n_records, n_rows, dim and n_grid must be positive");
+  if (!s->row_ptr || !s->row_g || !s->vals || !s->mask)
+    return fail(NJODE_E_BADARG, "null array in the store");
+  if ((s->att_min == nullptr) != (s->att_max == nullptr))
+    return fail(NJODE_E_BADARG, "att_min and att_max come together or not at all");
+  if (s->drop_unobserved)
+    return fail(NJODE_E_BADARG, "the validation layout belongs to a store that keeps every row "
+                                "(drop_unobserved = 0)");
+  if (!batch_idx || !val_ptr) return fail(NJODE_E_BADARG, "null batch_idx or val_ptr");
+  if (B <= 0 || max_val <= 0) return fail(NJODE_E_BADARG, "B and max_val must be positive");
+  if (g_cut < 0 || g_cut > s->n_grid)
+    return fail(NJODE_E_BADARG, "g_cut %d outside [0, %d]", g_cut, s->n_grid);
+  const int per = max_val < s->n_rows ? max_val : s->n_rows;
+  if ((long long)B * per > 0x7fffffffLL)
+    return fail(NJODE_E_BADARG, "B * min(max_val, n_rows) must fit 31 bits");
+  const size_t need = val_ws_bytes(B);
+  if (!ws || ws_bytes < need)
+    return fail(NJODE_E_WORKSPACE, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0,
+                need);
+  return NJODE_OK;
+}
+
 size_t table_bytes(int G, int B) { return (size_t)G * (size_t)B * sizeof(int32_t); }
 
 // what every entry point refuses about the store, the batch and the workspace
@@ -295,6 +420,49 @@ extern "C" int njode_records_heldout(const NjodeRecordStore* store, const int32_
   build_table(store, batch_idx, B, (int*)ws, 0, 0, nullptr, st);
   k_records_heldout<<<store->n_grid - g_hi, CB, 0, st>>>(*store, B, (const int*)ws, present, g_hi,
                                                         n_val, vals_val, mask_val);
+  HIP_TRY(hipGetLastError());
+  return NJODE_OK;
+}
+
+extern "C" int njode_records_val_bytes(int32_t B, size_t* out) {
+  if (!out) return fail(NJODE_E_BADARG, "null argument");
+  if (B <= 0) return fail(NJODE_E_BADARG, "B must be positive");
+  *out = val_ws_bytes(B);
+  return NJODE_OK;
+}
+
+extern "C" int njode_records_val_count(const NjodeRecordStore* store, const int32_t* batch_idx,
+                                       int32_t B, int32_t g_cut, int32_t max_val,
+                                       int32_t* val_ptr, void* ws, size_t ws_bytes,
+                                       njodeStream_t stream) {
+  if (const int rc = check_val_call(store, batch_idx, B, g_cut, max_val, val_ptr, ws, ws_bytes))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int* n_val = (int*)ws;
+  k_records_val_search<<<cdiv(B, CB), CB, 0, st>>>(*store, batch_idx, B, g_cut, max_val, n_val,
+                                                   n_val + B);
+  k_records_val_rank<<<cdiv(B, CB), CB, 0, st>>>(batch_idx, B, n_val, val_ptr);
+  HIP_TRY(hipGetLastError());
+  return NJODE_OK;
+}
+
+extern "C" int njode_records_val_fill(const NjodeRecordStore* store, const int32_t* batch_idx,
+                                      int32_t B, int32_t g_cut, int32_t max_val,
+                                      const int32_t* val_ptr, int32_t L, float* X_val,
+                                      float* M_val, int32_t* g_val, int32_t* index_val, void* ws,
+                                      size_t ws_bytes, njodeStream_t stream) {
+  if (const int rc = check_val_call(store, batch_idx, B, g_cut, max_val, val_ptr, ws, ws_bytes))
+    return rc;
+  if (L < 0) return fail(NJODE_E_BADARG, "negative L");
+  if (L > 0 && (!X_val || !M_val || !g_val || !index_val))
+    return fail(NJODE_E_BADARG, "null output");
+  if (L == 0) return NJODE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  int* n_val = (int*)ws;
+  k_records_val_search<<<cdiv(B, CB), CB, 0, st>>>(*store, batch_idx, B, g_cut, max_val, n_val,
+                                                   n_val + B);
+  k_records_val_fill<<<cdiv(B, CB / 64), CB, 0, st>>>(*store, B, n_val, n_val + B, val_ptr, L,
+                                                      X_val, M_val, g_val, index_val);
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
 }

@@ -18,7 +18,11 @@ elementwise), so a collate only ever orders and compares grid indices:
   repository's host route and the parity anchor of the kernels (needs no library);
 * ``collate`` / ``prepare_batches`` + ``fill_batch``: the same batches, bit for bit, built by the
   HIP kernels from the copy of the store in HBM.  No CPU fallback: they call into
-  ``libnjode_hip.so``.
+  ``libnjode_hip.so``;
+* ``collate_val_host`` / ``collate_val`` / ``prepare_val_batches``: the climate validation layout
+  (``ODE_Dataset(validation=True)``: observe up to ``T_val``, hold out each record's next
+  ``max_val_samples`` rows), in the same two routes.  It has methods of its own: ``LAYOUTS`` are
+  the two layouts of ``collate``.
 """
 import ctypes as C
 
@@ -190,6 +194,84 @@ class RecordDataset:
             out.update(times_val=self.grid[val_g].copy(), vals_val=vals_val, mask_val=mask_val)
         return out
 
+    # -- the climate validation layout, host route -----------------------------------------
+    def val_cut(self, T_val):
+        """``g_cut``: the number of grid points ``<= float32(T_val)`` -- the reference compares its
+        fp32 ``Time`` column with ``T_val``.  A row is observed if ``row_g < g_cut`` and held out
+        otherwise; 0 leaves nothing observed, ``n_grid`` nothing held out."""
+        if not np.isfinite(T_val):
+            raise ValueError('T_val must be finite, not {}'.format(T_val))
+        return int(np.searchsorted(self.grid, np.float64(np.float32(T_val)), side='right'))
+
+    def eligible(self, idx, T_val=150):
+        """The records of ``idx``, in their order, that a validation or test set keeps
+        (``ODE_Dataset.__init__:112-123``): at least one row ``<= T_val`` and one ``> T_val``."""
+        idx = _host_rows(idx, self.n_records).astype(np.int64)
+        g_cut = self.val_cut(T_val)
+        lo, hi = self.row_ptr[idx].astype(np.int64), self.row_ptr[idx + 1].astype(np.int64)
+        some = hi > lo
+        first = self.row_g[np.where(some, lo, 0)]
+        last = self.row_g[np.where(some, hi - 1, 0)]
+        return idx[some & (first < g_cut) & (last >= g_cut)]
+
+    def _check_val(self, T_val, max_val_samples):
+        if self.drop_unobserved:
+            raise ValueError('the validation layout belongs to the collate that keeps every row: '
+                             'a store with drop_unobserved=False')
+        if int(max_val_samples) != max_val_samples or max_val_samples < 1:
+            raise ValueError('max_val_samples must be a positive integer')
+        return self.val_cut(T_val), int(max_val_samples)
+
+    def _host_val_idx(self, idx):
+        idx = _host_rows(idx, self.n_records)
+        if len(idx) == 0:
+            raise ValueError('empty batch')
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError('a record appears twice in the batch: the validation layout maps '
+                             'records to batch positions')
+        return idx
+
+    def collate_val_host(self, idx, T_val=150, max_val_samples=3):
+        """The batch ``ODE_Dataset(validation=True, val_options={'T_val', 'max_val_samples'})`` +
+        ``custom_collate_fn`` build for records ``idx`` (batch order), on the host
+        (``data_utils_gru_ode_bayes.py:160-183, 257-265``).  The keys of ``collate_host``'s train
+        layout for the rows with time ``<= T_val``, and for the first ``max_val_samples`` later
+        rows of every record, sorted by (record, time): ``X_val`` / ``M_val`` fp32 CPU tensors
+        ``[L, D]``, ``times_val`` float64 ``[L]``, ``index_val`` int64 ``[L]`` (batch position of the
+        row's record); ``pat_idx`` the records.  ``climate_eval.evaluate_model`` takes the dict as
+        it is.  An empty observed part has zero rows and ``time_ptr = [0]``."""
+        g_cut, max_val = self._check_val(T_val, max_val_samples)
+        idx = self._host_val_idx(idx).astype(np.int64)
+        B, rb, rg, rid = self._batch_rows(idx)
+        mask = self.mask[rid]
+        # observed part: the climate collate restricted to g < g_cut (by time, then batch position)
+        sel = np.nonzero(rg < g_cut)[0]
+        sel = sel[np.lexsort((rb[sel], rg[sel]))]
+        obs_g = np.unique(rg[sel])
+        count = np.bincount(rg[sel], minlength=self.n_grid)
+        # held-out part: rank of a row among its record's rows after the cut
+        late = rg >= g_cut
+        n_rows = np.bincount(rb, minlength=B)
+        start = np.concatenate([[0], np.cumsum(n_rows)[:-1]])
+        rank = np.arange(len(rb)) - start[rb] - np.bincount(rb[~late], minlength=B)[rb]
+        val = np.nonzero(late & (rank < max_val))[0]
+        val = val[np.lexsort((rg[val], rb[val], idx[rb[val]]))]   # by record, (position,) time
+        return {
+            'times': self.grid[obs_g].copy(),
+            'time_ptr': np.concatenate([[0], np.cumsum(count[obs_g])]).astype(np.int64),
+            'X': torch.from_numpy(self._normalise(self.vals[rid[sel]], mask[sel])),
+            'M': torch.from_numpy(mask[sel].astype(np.float32)),
+            'obs_idx': torch.from_numpy(rb[sel].astype(np.int64)),
+            'n_obs_ot': torch.from_numpy(np.bincount(rb[sel], minlength=B).astype(np.int64)),
+            'start_X': torch.zeros(B, self.dim),
+            'batch_size': B,
+            'pat_idx': idx.tolist(),
+            'X_val': torch.from_numpy(self._normalise(self.vals[rid[val]], mask[val])),
+            'M_val': torch.from_numpy(mask[val].astype(np.float32)),
+            'times_val': self.grid[rg[val]].copy(),
+            'index_val': rb[val].astype(np.int64),
+        }
+
     # -- the device route ----------------------------------------------------------------
     def _need_device(self):
         if self._dev is None:
@@ -247,7 +329,8 @@ class RecordDataset:
 
     def fill_batch(self, prep):
         """Phase 2 (and, in test layout, 2b) for one descriptor of ``prepare_batches``: kernel
-        launches only, no host wait.  Same batch, bit for bit, as ``collate`` builds."""
+        launches only, no host wait.  Same batch, bit for bit, as ``collate`` builds.  A descriptor
+        of ``prepare_val_batches`` gives the batch ``collate_val`` builds."""
         self._need_device()
         L = _lib.lib()
         dev = self.device
@@ -278,7 +361,106 @@ class RecordDataset:
                     _ptr(vals_val) if n_val else null, _ptr(mask_val) if n_val else null,
                     _ptr(ws), ws.numel(), st))
                 out.update(times_val=prep['times_val'], vals_val=vals_val, mask_val=mask_val)
+            if prep['layout'] == 'validation':
+                n_val = prep['L']
+                X_val = torch.empty((n_val, D), dtype=f32, device=dev)
+                M_val = torch.empty((n_val, D), dtype=f32, device=dev)
+                g_val = torch.empty(n_val, dtype=i32, device=dev)
+                index_val = torch.empty(n_val, dtype=i32, device=dev)
+                ws_val = prep['ws_val']
+                _lib.check(L.njode_records_val_fill(
+                    C.byref(self._store), _ptr(prep['idx']), B, prep['g_hi'], prep['max_val'],
+                    _ptr(prep['val_ptr']), n_val, _ptr(X_val) if n_val else null,
+                    _ptr(M_val) if n_val else null, _ptr(g_val) if n_val else null,
+                    _ptr(index_val) if n_val else null, _ptr(ws_val), ws_val.numel(), st))
+                out.update(X_val=X_val, M_val=M_val, index_val=index_val,
+                           times_val=self._grid_device()[g_val.long()], pat_idx=prep['pat_idx'])
         return out
+
+    def _grid_device(self):
+        if self._dev.get('grid') is None:
+            self._dev['grid'] = torch.from_numpy(self.grid).to(self.device)
+        return self._dev['grid']
+
+    def _prepare_val(self, idx_dev, sizes, pat_idx, g_cut, max_val):
+        L = _lib.lib()
+        dev = self.device
+        n, G = len(sizes), self.n_grid
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        # per batch [present G | count G | val_ptr B + 1], all batches in one buffer: one copy back
+        seg = np.concatenate([[0], np.cumsum([2 * G + B + 1 for B in sizes])])
+        buf = torch.empty(int(seg[-1]), dtype=torch.int32, device=dev)
+        ws = self._ws(max(sizes))
+        need = C.c_size_t(0)
+        _lib.check(L.njode_records_val_bytes(max(sizes), C.byref(need)))
+        ws_val = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        parts = []
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for i in range(n):
+                lo, s0, B = int(offs[i]), int(seg[i]), sizes[i]
+                flags = buf[s0:s0 + 2 * G].view(2, G)
+                val_ptr = buf[s0 + 2 * G:s0 + 2 * G + B + 1]
+                idx_i = C.c_void_p(idx_dev.data_ptr() + 4 * lo)
+                _lib.check(L.njode_records_count(
+                    C.byref(self._store), idx_i, B, _ptr(flags[0]), _ptr(flags[1]), _ptr(ws),
+                    ws.numel(), st))
+                _lib.check(L.njode_records_val_count(
+                    C.byref(self._store), idx_i, B, g_cut, max_val, _ptr(val_ptr), _ptr(ws_val),
+                    ws_val.numel(), st))
+                parts.append((flags, val_ptr))
+            host = buf.cpu().numpy()                                      # one copy, one wait
+        out = []
+        for i in range(n):
+            lo, hi, s0, B = int(offs[i]), int(offs[i + 1]), int(seg[i]), sizes[i]
+            present, count = host[s0:s0 + G], host[s0 + G:s0 + 2 * G]
+            obs_g = np.nonzero(present[:g_cut])[0]
+            time_ptr = np.concatenate([[0], np.cumsum(count[obs_g])]).astype(np.int64)
+            out.append({'times': self.grid[obs_g].copy(), 'time_ptr': time_ptr,
+                        'idx': idx_dev[lo:hi], 'B': B, 'flags': parts[i][0], 'g_hi': g_cut,
+                        'layout': 'validation', 'ws': ws, 'ws_val': ws_val,
+                        'val_ptr': parts[i][1], 'L': int(host[s0 + 2 * G + B]),
+                        'max_val': max_val, 'pat_idx': pat_idx[i]})
+        return out
+
+    def prepare_val_batches(self, idx_list, T_val=150, max_val_samples=3):
+        """``prepare_batches`` for the climate validation layout: ONE upload of the indices, the
+        count kernels of the observed and of the held-out part of all batches enqueued back to
+        back, ONE copy back (per-time counts and the number of held-out rows ``L`` of every batch),
+        ONE wait.  Returns one descriptor per batch for ``fill_batch``.  ``ValueError``, before
+        anything is uploaded or launched: a record outside the store or twice in a batch, an empty
+        batch, ``max_val_samples < 1``, a non-finite ``T_val``, a store with
+        ``drop_unobserved=True``."""
+        self._need_device()
+        g_cut, max_val = self._check_val(T_val, max_val_samples)
+        lists = [self._host_val_idx(ix) for ix in idx_list]
+        if not lists:
+            raise ValueError('empty batch')
+        idx_dev = torch.from_numpy(np.concatenate(lists)).to(self.device)
+        return self._prepare_val(idx_dev, [len(ix) for ix in lists], [ix.tolist() for ix in lists],
+                                 g_cut, max_val)
+
+    def collate_val(self, idx, T_val=150, max_val_samples=3):
+        """``collate_val_host`` on the GPU: ``X``, ``M``, ``obs_idx`` (int32), ``n_obs_ot`` (int32),
+        ``start_X``, ``X_val``, ``M_val``, ``index_val`` (int32) and ``times_val`` (float64, the
+        device copy of ``grid`` gathered at the rows' grid indices) are device tensors; ``times`` and
+        ``time_ptr`` numpy arrays.  One host wait, like ``collate``.
+
+        Records given on the host are checked like ``prepare_val_batches`` checks them.  A device
+        tensor is used as it is, unchecked: an entry outside the store counts as a record without
+        rows, and of a record that appears twice the held-out rows are listed by batch position."""
+        self._need_device()
+        g_cut, max_val = self._check_val(T_val, max_val_samples)
+        if torch.is_tensor(idx) and idx.device.type != 'cpu':
+            idx_dev = idx.to(self.device).to(torch.int32).contiguous().reshape(-1)
+            if idx_dev.numel() == 0:
+                raise ValueError('empty batch')
+            pat_idx = idx_dev
+        else:
+            host = self._host_val_idx(idx)
+            idx_dev, pat_idx = torch.from_numpy(host).to(self.device), host.tolist()
+        return self.fill_batch(
+            self._prepare_val(idx_dev, [idx_dev.numel()], [pat_idx], g_cut, max_val)[0])
 
     def collate(self, idx, layout='train'):
         """``collate_host`` on the GPU: ``X``, ``M``, ``obs_idx`` (int32), ``n_obs_ot`` (int32),

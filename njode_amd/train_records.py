@@ -18,6 +18,10 @@ Reproduces the compute semantics of the reference harness ``NJODE/physionet_trai
 Batches follow ``parallel.epoch_permutation`` like ``train.train``.  The fused step
 (``NJODE.loss_and_grad`` + ``FusedAdam``) is the default; ``fused=False`` drives the model like
 the reference (``loss.backward()`` + ``torch.optim.Adam``).  Single process only.
+
+``train_climate_records`` is the same loop for the third entry point of the reference,
+``NJODE/climate_train.py:356-488``: a validation and a test set, each one batch in the climate
+validation layout, scored after every epoch (``climate_eval.evaluate_model_device``).
 """
 import csv
 import os
@@ -26,7 +30,7 @@ import time
 import numpy as np
 import torch
 
-from . import models, parallel, physionet_eval, synthetic_physionet
+from . import climate_eval, models, parallel, physionet_eval, synthetic_physionet
 
 METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss', 'eval_metric',
                 'eval_metric_2']
@@ -42,6 +46,97 @@ def _upload(b, device):
     d['obs_idx'] = b['obs_idx'].to(device, torch.int32)
     d['n_obs_ot'] = b['n_obs_ot'].to(device, torch.int32)
     return d
+
+
+def _epoch_steps(model, optimizer, dataset, lists, prepared, dev, delta_t, T, fused, plan_ahead):
+    """The optimizer steps of one epoch on the train-layout batches of the records ``lists``
+    (``prepared``: their ``prepare_batches`` descriptors, or None for the host collate), the next
+    batch collated -- and its plan prefetched -- beside the current step.  Returns the last
+    batch's loss."""
+    def prepare(s):
+        if prepared is not None:
+            return dataset.fill_batch(prepared[s])
+        return _upload(dataset.collate_host(lists[s], 'train'), dev)
+
+    loss = None
+    nxt = prepare(0)
+    for s in range(len(lists)):
+        d = nxt
+        nxt = prepare(s + 1) if s + 1 < len(lists) else None
+        # (the conditions of train.train; a masked model never defers its plan)
+        if plan_ahead and fused and nxt is not None and \
+                (nxt['batch_size'] <= 512 or nxt['batch_size'] >= 4096):
+            model.prefetch_plan(nxt['times'], nxt['time_ptr'], nxt['X'], nxt['obs_idx'], delta_t,
+                                T, nxt['start_X'], nxt['n_obs_ot'], M=nxt['M'], need_hT=True)
+        args = (d['times'], d['time_ptr'], d['X'], d['obs_idx'], delta_t, T, d['start_X'],
+                d['n_obs_ot'])
+        optimizer.zero_grad()
+        if fused:
+            _, loss = model.loss_and_grad(*args, M=d['M'])
+        else:
+            _, loss = model(*args, return_path=False, get_loss=True, M=d['M'])
+            loss.backward()
+        optimizer.step()
+    return loss
+
+
+class _Run:
+    """Checkpoints, metric file and resume of one model id under ``model_path`` (None: nothing is
+    written) -- what the two loops below share.  ``columns[5]`` is the ``eval_metric`` the best
+    checkpoint follows."""
+
+    def __init__(self, model_path, model_id, columns, log):
+        self.columns, self.log = columns, log
+        self.best_eval_metric = np.inf
+        self.path_last = self.path_best = self.metric_file = None
+        self.saved_rows, self.pending = [], []
+        if model_path is not None:
+            model_dir = os.path.join(model_path, 'id-{}'.format(model_id))
+            self.path_last = os.path.join(model_dir, 'last_checkpoint')
+            self.path_best = os.path.join(model_dir, 'best_checkpoint')
+            self.metric_file = os.path.join(model_dir, 'metric_id-{}.csv'.format(model_id))
+            os.makedirs(model_dir, exist_ok=True)
+
+    def resume(self, model, optimizer, dev, resume_training, load_best):
+        if self.metric_file is None or not resume_training:
+            return
+        path = self.path_best if load_best else self.path_last
+        if not os.path.exists(os.path.join(path, 'checkpt.tar')):
+            return
+        models.get_ckpt_model(path, model, optimizer, dev)
+        if os.path.exists(self.metric_file):
+            with open(self.metric_file) as f:
+                self.saved_rows = [[float(x) for x in r[1:]] for r in list(csv.reader(f))[1:]]
+            if self.saved_rows:
+                self.best_eval_metric = min(r[5] for r in self.saved_rows)
+        model.epoch += 1
+        model.weight_decay_step()
+
+    def write_metrics(self):
+        # pandas' DataFrame.to_csv layout: unnamed index column first
+        with open(self.metric_file, 'w', newline='') as f:
+            wr = csv.writer(f)
+            wr.writerow([''] + self.columns)
+            for i, r in enumerate(self.saved_rows):
+                wr.writerow([i] + r)
+
+    def new_best(self, model, optimizer, mse_val):
+        """``best_checkpoint`` when ``eval_metric`` improves."""
+        if self.metric_file is None or not mse_val < self.best_eval_metric:
+            return
+        self.log('save new best model: last-best-metric: {:.5f}, new-best-metric: {:.5f}, '
+                 'epoch: {}'.format(self.best_eval_metric, mse_val, model.epoch))
+        models.save_checkpoint(model, optimizer, self.path_best, model.epoch)
+        self.best_eval_metric = mse_val
+
+    def end_of_epoch(self, model, optimizer, row, save_every):
+        """The epoch's metric row; ``last_checkpoint`` + metric file every ``save_every`` epochs."""
+        self.pending.append(row)
+        if self.metric_file is not None and model.epoch % save_every == 0:
+            self.saved_rows.extend(self.pending)
+            self.pending = []
+            self.write_metrics()
+            models.save_checkpoint(model, optimizer, self.path_last, model.epoch)
 
 
 def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learning_rate=1e-3,
@@ -93,33 +188,8 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
     else:
         test_batches = [_upload(dataset.collate_host(ix, 'test'), dev) for ix in test_lists]
 
-    best_eval_metric = np.inf
-    path_last = path_best = metric_file = None
-    saved_rows = []
-    if model_path is not None:
-        model_dir = os.path.join(model_path, 'id-{}'.format(model_id))
-        path_last = os.path.join(model_dir, 'last_checkpoint')
-        path_best = os.path.join(model_dir, 'best_checkpoint')
-        metric_file = os.path.join(model_dir, 'metric_id-{}.csv'.format(model_id))
-        os.makedirs(model_dir, exist_ok=True)
-        if resume_training and os.path.exists(os.path.join(
-                path_best if load_best else path_last, 'checkpt.tar')):
-            models.get_ckpt_model(path_best if load_best else path_last, model, optimizer, dev)
-            if os.path.exists(metric_file):
-                with open(metric_file) as f:
-                    saved_rows = [[float(x) for x in r[1:]] for r in list(csv.reader(f))[1:]]
-                if saved_rows:
-                    best_eval_metric = min(r[5] for r in saved_rows)
-            model.epoch += 1
-            model.weight_decay_step()
-
-    def write_metrics():
-        # pandas' DataFrame.to_csv layout: unnamed index column first
-        with open(metric_file, 'w', newline='') as f:
-            wr = csv.writer(f)
-            wr.writerow([''] + METR_COLUMNS)
-            for i, r in enumerate(saved_rows):
-                wr.writerow([i] + r)
+    run = _Run(model_path, model_id, METR_COLUMNS, log)
+    run.resume(model, optimizer, dev, resume_training, load_best)
 
     def plan_epoch(epoch):
         order = train_idx[parallel.epoch_permutation(len(train_idx), epoch, shuffle_seed)]
@@ -127,36 +197,13 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
         return lists, dataset.prepare_batches(lists, 'train') if device_collate else None
 
     plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
-    metrics, pending, epoch_plan = [], [], {}
+    metrics, epoch_plan = [], {}
     while model.epoch <= epochs:
         t0 = time.time()
         model.train()
         lists, prepared = epoch_plan.pop(model.epoch, None) or plan_epoch(model.epoch)
-
-        def prepare(s):
-            if device_collate:
-                return dataset.fill_batch(prepared[s])
-            return _upload(dataset.collate_host(lists[s], 'train'), dev)
-
-        loss = None
-        nxt = prepare(0)
-        for s in range(len(lists)):
-            d = nxt
-            nxt = prepare(s + 1) if s + 1 < len(lists) else None
-            # (the conditions of train.train; a masked model never defers its plan)
-            if plan_ahead and fused and nxt is not None and \
-                    (nxt['batch_size'] <= 512 or nxt['batch_size'] >= 4096):
-                model.prefetch_plan(nxt['times'], nxt['time_ptr'], nxt['X'], nxt['obs_idx'], delta_t,
-                                    T, nxt['start_X'], nxt['n_obs_ot'], M=nxt['M'], need_hT=True)
-            args = (d['times'], d['time_ptr'], d['X'], d['obs_idx'], delta_t, T, d['start_X'],
-                    d['n_obs_ot'])
-            optimizer.zero_grad()
-            if fused:
-                _, loss = model.loss_and_grad(*args, M=d['M'])
-            else:
-                _, loss = model(*args, return_path=False, get_loss=True, M=d['M'])
-                loss.backward()
-            optimizer.step()
+        loss = _epoch_steps(model, optimizer, dataset, lists, prepared, dev, delta_t, T, fused,
+                            plan_ahead)
         # the next epoch's order and collate counts, queued behind this epoch's steps: their one
         # host wait is the end-of-epoch wait the loop needs anyway
         if device_collate and model.epoch + 1 <= epochs:
@@ -174,18 +221,109 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
                                           mse_val_2))
         row = [model.epoch, train_time, eval_time, train_loss, loss_val, mse_val, mse_val_2]
         metrics.append(row)
-        pending.append(row)
-        if model_path is not None:
-            if mse_val < best_eval_metric:
-                log('save new best model: last-best-metric: {:.5f}, new-best-metric: {:.5f}, '
-                    'epoch: {}'.format(best_eval_metric, mse_val, model.epoch))
-                models.save_checkpoint(model, optimizer, path_best, model.epoch)
-                best_eval_metric = mse_val
-            if model.epoch % save_every == 0:
-                saved_rows.extend(pending)
-                pending = []
-                write_metrics()
-                models.save_checkpoint(model, optimizer, path_last, model.epoch)
+        run.new_best(model, optimizer, mse_val)
+        run.end_of_epoch(model, optimizer, row, save_every)
+        model.epoch += 1
+        model.weight_decay_step()
+    return model, metrics
+
+
+CLIMATE_METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss',
+                        'eval_metric', 'test_loss', 'test_metric']
+
+
+def train_climate_records(dataset, train_idx, val_idx, test_idx, epochs=1, batch_size=100,
+                          learning_rate=1e-3, hidden_size=10, bias=True, dropout_rate=0.1,
+                          ode_nn=NN, readout_nn=NN, enc_nn=NN, use_rnn=False, solver='euler',
+                          weight=0.5, weight_decay=1., T=climate_eval.CLIMATE_T,
+                          T_val=climate_eval.CLIMATE_T_VAL, max_val_samples=3, device='cuda',
+                          fused=True, device_collate=True, shuffle_seed=0, log=print,
+                          model_path=None, model_id=1, save_every=1, resume_training=False,
+                          load_best=False, plan_ahead=True, init_state=None, **options):
+    """The compute semantics of ``NJODE/climate_train.py:356-488`` on a ``records.RecordDataset``
+    of climate records (every row kept, values raw): train on whole records ``train_idx`` in the
+    train layout; after every epoch ``evaluate_model`` on the validation set and on the test set,
+    each ONE batch of its eligible records (``dataset.eligible``: a row up to ``T_val`` and a row
+    after it) in the validation layout (observe up to ``T_val``, score the next
+    ``max_val_samples`` rows of every record), collated once, in the records' order.  Returns
+    ``(model, metrics)`` with one row of ``CLIMATE_METR_COLUMNS`` per epoch; ``best_checkpoint``
+    follows the validation MSE.  ``delta_t`` is the reference's option (default 0.1).
+
+    ``device_collate``, ``fused``, ``resume_training`` / ``load_best`` as in ``train_records``.
+    ``ValueError`` for an empty eligible validation or test set and under a process group of more
+    than one rank."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() \
+            and torch.distributed.get_world_size() > 1:
+        raise ValueError('train_climate_records is single process: multi-GPU record training is '
+                         'not offered')
+    train_idx = np.asarray(train_idx, dtype=np.int64).reshape(-1)
+    if len(train_idx) == 0 or batch_size <= 0:
+        raise ValueError('train_idx and batch_size must not be empty')
+    if device_collate and dataset.device is None:
+        raise ValueError('device_collate needs a RecordDataset resident on the GPU')
+    val_idx, test_idx = dataset.eligible(val_idx, T_val), dataset.eligible(test_idx, T_val)
+    if len(val_idx) == 0 or len(test_idx) == 0:
+        raise ValueError('no record of the validation or of the test set has a row up to T_val = '
+                         '{} and a row after it'.format(T_val))
+    dev = torch.device(device)
+    model_opts = dict(options)
+    delta_t = model_opts.pop('delta_t', climate_eval.CLIMATE_DELTA_T)
+    model_opts['masked'] = True
+    model_opts['device_outputs'] = True
+    dim = dataset.dim
+    torch.manual_seed(0)
+    model = models.NJODE(dim, hidden_size, dim, ode_nn, readout_nn, enc_nn, use_rnn, bias=bias,
+                         dropout_rate=dropout_rate, solver=solver, weight=weight,
+                         weight_decay=weight_decay, options=model_opts).to(dev)
+    if init_state is not None:
+        model.load_state_dict(init_state)
+    if fused:
+        optimizer = models.FusedAdam(model, lr=learning_rate, weight_decay=0.0005)
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate, weight_decay=0.0005)
+
+    # the validation and the test set never change: one batch each, collated once
+    if device_collate:
+        val_batch, test_batch = (dataset.fill_batch(p) for p in dataset.prepare_val_batches(
+            [val_idx, test_idx], T_val, max_val_samples))
+    else:
+        val_batch, test_batch = (_upload(dataset.collate_val_host(ix, T_val, max_val_samples), dev)
+                                 for ix in (val_idx, test_idx))
+
+    run = _Run(model_path, model_id, CLIMATE_METR_COLUMNS, log)
+    run.resume(model, optimizer, dev, resume_training, load_best)
+
+    def plan_epoch(epoch):
+        order = train_idx[parallel.epoch_permutation(len(train_idx), epoch, shuffle_seed)]
+        lists = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+        return lists, dataset.prepare_batches(lists, 'train') if device_collate else None
+
+    plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
+    metrics, epoch_plan = [], {}
+    while model.epoch <= epochs:
+        t0 = time.time()
+        model.train()
+        lists, prepared = epoch_plan.pop(model.epoch, None) or plan_epoch(model.epoch)
+        loss = _epoch_steps(model, optimizer, dataset, lists, prepared, dev, delta_t, T, fused,
+                            plan_ahead)
+        if device_collate and model.epoch + 1 <= epochs:
+            epoch_plan[model.epoch + 1] = plan_epoch(model.epoch + 1)
+        torch.cuda.synchronize(dev)
+        train_time = time.time() - t0
+
+        t0 = time.time()
+        loss_val, mse_val = climate_eval.evaluate_model_device(model, [val_batch], dev, delta_t, T)
+        eval_time = time.time() - t0
+        train_loss = float(loss.detach())
+        log("epoch {}, weight={:.5f}, train-loss={:.5f}, eval-loss={:.5f}, eval-metric={:.5f}".format(
+            model.epoch, model.weight, train_loss, loss_val, mse_val))
+        run.new_best(model, optimizer, mse_val)
+        loss_test, mse_test = climate_eval.evaluate_model_device(model, [test_batch], dev, delta_t, T)
+        log("test-loss={:.5f}, test-metric={:.5f}".format(loss_test, mse_test))
+        row = [model.epoch, train_time, eval_time, train_loss, loss_val, mse_val, loss_test,
+               mse_test]
+        metrics.append(row)
+        run.end_of_epoch(model, optimizer, row, save_every)
         model.epoch += 1
         model.weight_decay_step()
     return model, metrics
