@@ -40,7 +40,7 @@
  *     stated at each entry point and are held to them in the same way (tile kernels do not touch
  *     padded rows behind batch_size or n_obs).  `workspace` and `plan` must be aligned to 256
  *     bytes: the library lays its sub-buffers out at multiples of 256 bytes from the base
- *     (Layout::take, njode_api.hip / njode_gen.hip) and reads them with 8-byte words and 16-byte
+ *     (Arena::take, njode_amd/csrc/njode_hostlib.h) and reads them with 8-byte words and 16-byte
  *     vectors.  Every other array (parameters, batch, outputs) has only been tested at the alignment
  *     of a device allocation's pointer: tests/test_hip_buffer_bounds.py calls every entry point at
  *     exactly these sizes between guard bands with EVERY array 256-byte aligned, and no test hands

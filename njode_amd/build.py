@@ -66,13 +66,35 @@ def _hipcc():
     return 'hipcc'
 
 
-def _digest(files, extra=''):
+def _dep_files(obj):
+    """The repository's own files among those the compiler read for ``obj`` (its depfile,
+    written by -MD -MF), or None when there is no depfile: such an object is stale."""
+    try:
+        with open(obj + '.d') as f:
+            text = f.read()
+    except OSError:
+        return None
+    words = text.replace('\\\n', ' ').split()
+    root = os.path.dirname(HERE) + os.sep
+    return sorted({os.path.abspath(w) for w in words if not w.endswith(':')
+                   and os.path.abspath(w).startswith(root)})
+
+
+def _digest(obj, cmd):
+    """Digest of everything ``obj`` was compiled from: the files of its depfile and its command
+    line.  None: no depfile, or a file it names is gone."""
+    files = _dep_files(obj)
+    if files is None:
+        return None
     h = hashlib.sha256()
     for path in files:
-        with open(path, 'rb') as f:
-            h.update(os.path.basename(path).encode())
-            h.update(f.read())
-    h.update(extra.encode())
+        try:
+            with open(path, 'rb') as f:
+                h.update(os.path.basename(path).encode())
+                h.update(f.read())
+        except OSError:
+            return None
+    h.update(' '.join(cmd).encode())
     return h.hexdigest()
 
 
@@ -135,35 +157,7 @@ def build(force=False, jobs=None, verbose=True):
     common = [cc, '--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-c',
               '-Rpass-analysis=kernel-resource-usage']
     common += os.environ.get('NJODE_EXTRA_FLAGS', '').split()   # kernel experiments
-    hdr = os.path.join(os.path.dirname(HERE), 'include', 'njode_hip.h')
-    hdr_prod = os.path.join(os.path.dirname(HERE), 'include', 'njode_producer.h')
-    hdr_self = os.path.join(os.path.dirname(HERE), 'include', 'njode_selftest.h')
-    hdr_proto = os.path.join(os.path.dirname(HERE), 'include', 'njode_protocol.h')
-    hdr_rec = os.path.join(os.path.dirname(HERE), 'include', 'njode_records.h')
-    kernel_deps = [os.path.join(CSRC, n) for n in
-                   ('njode_cfg.hip', 'njode_host.h', 'njode_kernels.h', 'njode_device.h',
-                    'njode_mfma.h', 'njode_mfma_rows.h', 'njode_lockstep_bwd.h',
-                    'njode_mfma_lockstep.h', 'njode_mfma_split.h', 'njode_ode2.h',
-                    'njode_mfma_lock4.h', 'njode_plan.h', 'njode_route.h')] + [hdr]
-    chain_deps = kernel_deps + [os.path.join(CSRC, n) for n in ('njode_chain.h', 'njode_dpp.h', 'njode_chain_seg.h', 'njode_chain_dw.h')]
-    gen_deps = [os.path.join(CSRC, n) for n in
-                ('njode_gen.hip', 'njode_gen.h', 'njode_gen_seg.h', 'njode_gen_host.h', 'njode_device.h',
-                 'njode_error.h')] + [hdr]
-    api_deps = [os.path.join(CSRC, n) for n in
-                ('njode_api.hip', 'njode_gen_host.h', 'njode_host.h', 'njode_kernels.h', 'njode_device.h',
-                 'njode_mfma.h', 'njode_mfma_rows.h', 'njode_lockstep_bwd.h',
-                 'njode_mfma_lockstep.h', 'njode_mfma_split.h', 'njode_ode2.h',
-                 'njode_mfma_lock4.h', 'njode_error.h', 'njode_plan.h', 'njode_route.h',
-                 '_generated_cfgs.inc')] + [hdr, hdr_self]
-    prod_deps = [os.path.join(CSRC, n) for n in ('njode_producer.hip', 'njode_error.h')] + [
-        hdr, hdr_prod]
-    ce_deps = [os.path.join(CSRC, n) for n in ('njode_condexp.hip', 'njode_error.h')] + [
-        hdr, hdr_prod]
-    proto_deps = [os.path.join(CSRC, n) for n in ('njode_protocol.hip', 'njode_error.h')] + [
-        hdr, hdr_proto]
-    rec_deps = [os.path.join(CSRC, n) for n in ('njode_records.hip', 'njode_error.h')] + [
-        hdr, hdr_rec]
-    tasks = []   # (object, command, digest)
+    tasks = []   # (object, command)
     for i, (d, h, do, nh, w, act, masked, curt, res, rnn) in enumerate(cfgs):
         for part in range(6):
             obj = os.path.join(OBJ, 'cfg{}_{}.o'.format(i, part))
@@ -172,51 +166,50 @@ def build(force=False, jobs=None, verbose=True):
                     '-DNJ_W={}'.format(max(w, 1)), '-DNJ_ACT={}'.format(act),
                     '-DNJ_MASKED={}'.format(masked), '-DNJ_CURT={}'.format(curt),
                     '-DNJ_RES={}'.format(res), '-DNJ_ACC_TANH={}'.format(masked), '-DNJ_RNN={}'.format(rnn)]
-            cmd = common + defs + [os.path.join(CSRC, 'njode_cfg.hip'), '-o', obj]
-            tasks.append((obj, cmd, _digest(chain_deps if part >= 4 else kernel_deps, ' '.join(cmd))))
-    api_obj = os.path.join(OBJ, 'api.o')
-    cmd = common + [os.path.join(CSRC, 'njode_api.hip'), '-o', api_obj]
-    tasks.append((api_obj, cmd, _digest(api_deps, ' '.join(cmd))))
-    gen_obj = os.path.join(OBJ, 'gen.o')
-    cmd = common + [os.path.join(CSRC, 'njode_gen.hip'), '-o', gen_obj]
-    tasks.append((gen_obj, cmd, _digest(gen_deps, ' '.join(cmd))))
+            tasks.append((obj, common + defs + [os.path.join(CSRC, 'njode_cfg.hip')]))
+    for unit in ('api', 'planner', 'prof', 'gen'):
+        tasks.append((os.path.join(OBJ, unit + '.o'), common + [os.path.join(CSRC, 'njode_{}.hip'.format(unit))]))
     # the batch producer spells out the reference's float64 expression trees: no contraction
-    prod_obj = os.path.join(OBJ, 'producer.o')
-    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_producer.hip'), '-o', prod_obj]
-    tasks.append((prod_obj, cmd, _digest(prod_deps, ' '.join(cmd))))
+    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_producer.hip')]
+    tasks.append((os.path.join(OBJ, 'producer.o'), cmd))
     # ... and so does the analytic conditional expectation (the host walk's y * a + c, unfused)
-    ce_obj = os.path.join(OBJ, 'condexp.o')
-    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_condexp.hip'), '-o', ce_obj]
-    tasks.append((ce_obj, cmd, _digest(ce_deps, ' '.join(cmd))))
+    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_condexp.hip')]
+    tasks.append((os.path.join(OBJ, 'condexp.o'), cmd))
     # ... and the evaluation protocols (numpy's fp32 terms: subtract, square, multiply, unfused)
-    proto_obj = os.path.join(OBJ, 'protocol.o')
-    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_protocol.hip'), '-o', proto_obj]
-    tasks.append((proto_obj, cmd, _digest(proto_deps, ' '.join(cmd))))
+    cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_protocol.hip')]
+    tasks.append((os.path.join(OBJ, 'protocol.o'), cmd))
     # ... and the record collate (torch's fp32 (v - att_min) / att_max: one subtraction, one
     # correctly rounded division)
-    rec_obj = os.path.join(OBJ, 'records.o')
     cmd = common + ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
-                    os.path.join(CSRC, 'njode_records.hip'), '-o', rec_obj]
-    tasks.append((rec_obj, cmd, _digest(rec_deps, ' '.join(cmd))))
+                    os.path.join(CSRC, 'njode_records.hip')]
+    tasks.append((os.path.join(OBJ, 'records.o'), cmd))
+    # what a unit depends on is what the compiler read for it (-MD), not a list kept by hand
+    tasks = [(obj, cmd + ['-MD', '-MF', obj + '.d', '-o', obj]) for obj, cmd in tasks]
+
+    def restamp(t):
+        d = _digest(*t)
+        if d is not None:
+            with open(t[0] + '.stamp', 'w') as f:
+                f.write(d)
+
     if os.environ.get('NJODE_RESTAMP'):   # maintainer aid: adopt the objects on disk as current
         for t in tasks:
             if os.path.exists(t[0]):
-                with open(t[0] + '.stamp', 'w') as f:
-                    f.write(t[2])
+                restamp(t)
 
     def stale(t):
         stamp = t[0] + '.stamp'
         return (force or not os.path.exists(t[0]) or not os.path.exists(stamp)
-                or open(stamp).read() != t[2])
+                or open(stamp).read() != _digest(*t))
 
     todo = [t for t in tasks if stale(t)]
     parts_only = os.environ.get('NJODE_PARTS_ONLY', '').strip()   # maintainer aid, e.g. "0": a change
     if parts_only:                                                 # that only touches those parts
-        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + ('api.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o')
+        keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + (
+            'api.o', 'planner.o', 'prof.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
-                with open(t[0] + '.stamp', 'w') as f:
-                    f.write(t[2])
+                restamp(t)
         todo = [t for t in todo if t[0].endswith(keep) or not os.path.exists(t[0])]
     if not todo and os.path.exists(LIB) and not force:
         if verbose:
@@ -234,8 +227,7 @@ def build(force=False, jobs=None, verbose=True):
         res, rest = _parse_resources(out)
         with open(t[0] + '.res.json', 'w') as f:
             json.dump(res, f)
-        with open(t[0] + '.stamp', 'w') as f:
-            f.write(t[2])
+        restamp(t)
         return rest
 
     # heaviest units first (masked 41-dim lockstep kernels dominate the wall time)

@@ -278,7 +278,7 @@ static hipError_t seg_forward_t(const KArgs& a, const Route& r, hipStream_t st) 
     // forward, on a stream of their own, and share the chip with it
     if (r.tails_side) {
       // the tails' stream waits for the encoder rows and for the plan's tail order: the latter is
-      // on that stream itself (njode_api.hip, build_plan) or, failing that, on `st` -- then e0,
+      // on that stream itself (njode_planner.hip, build_plan) or, failing that, on `st` -- then e0,
       // which the helper stream consumed above, is recorded again here to stand for "everything
       // `st` has enqueued by now"
       (void)hipStreamWaitEvent(side->st2, side->e1, 0);

@@ -14,40 +14,15 @@
 // float atomics), so two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 
 #include "../../include/njode_producer.h"
-#include "njode_error.h"
-
-namespace njode {
-void prof_mark(const char* name, hipStream_t st, bool begin);   // njode_api.hip
-}
+#include "njode_hostlib.h"
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  njode::set_error_v(code, fmt, ap);
-  va_end(ap);
-  return code;
-}
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(NJODE_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
+using namespace njode;
 
-struct Prof {
-  const char* name;
-  hipStream_t st;
-  Prof(const char* n, hipStream_t s) : name(n), st(s) { njode::prof_mark(name, st, true); }
-  ~Prof() { njode::prof_mark(name, st, false); }
-};
-
-inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
 inline size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 
 constexpr int WB = 256;          // workgroup of the walk (4 waves)
@@ -67,7 +42,7 @@ Layout layout(long long B, long long n_obs, long long nt, long long K, long long
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += pad256(bytes); return at; };
   L.n_rows = 1 + K + nt;
-  L.n_blocks = cdivl(B * dim, WB);
+  L.n_blocks = cdiv(B * dim, WB);
   L.step_dt = take((size_t)K * 8);
   L.step_t = take((size_t)K * 8);
   L.a = take((size_t)K * 8);
@@ -406,18 +381,18 @@ int cond_exp_run(const NjodeSde* sde, const Stages* sg, int dim, int mode, const
   if (nt > 0) HIP_TRY(hipMemcpyAsync(d_kj, sched->k_jump, (size_t)nt * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_tp, sched->time_ptr, (size_t)(nt + 1) * 4, hipMemcpyHostToDevice, st));
   if (nt > 0) HIP_TRY(hipMemsetAsync(dense, 0xFF, (size_t)nt * B * 4, st));
-  const int table_grid = (int)cdivl(K + nt > 0 ? K + nt : 1, 256);
+  const int table_grid = cdiv(K + nt > 0 ? K + nt : 1, 256);
   if (sg)
     k_cond_exp_table_staged<<<table_grid, 256, 0, st>>>(*sg, K, nt, d_dt, d_t, d_kj, a, c, a1, c1, desc);
   else
     k_cond_exp_table<<<table_grid, 256, 0, st>>>(*sde, K, nt, d_dt, d_t, d_kj, a, c, desc);
   if (n_obs > 0)
-    k_cond_exp_rows<<<(int)cdivl(n_obs, 256), 256, 0, st>>>(d_tp, nt, n_obs, batch->obs_idx, B, dense);
+    k_cond_exp_rows<<<cdiv(n_obs, 256), 256, 0, st>>>(d_tp, nt, n_obs, batch->obs_idx, B, dense);
   const bool want_loss = opt_loss && n_obs > 0;
   // (a row no path walks -- obs_idx outside the batch -- must not leave its squares unwritten)
   if (want_loss) HIP_TRY(hipMemsetAsync(sq_rows, 0, (size_t)n_obs * dim * 8, st));
   {
-    Prof ps("k_cond_exp_walk", st);
+    ProfScope ps("k_cond_exp_walk", st);
 #define NJ_MODE(M)                                                                                  \
   launch_walk<M>(path_y != nullptr, want_loss, sq_diff != nullptr, (int)L.n_blocks, st, B, dim,      \
                  (int)L.n_rows, batch->start_X, batch->X, desc, dense, a, c, a1, c1, pred, path_y,   \
@@ -431,7 +406,7 @@ int cond_exp_run(const NjodeSde* sde, const Stages* sg, int dim, int mode, const
     if (n_obs > 0) {
       const double eps = 1e-10;
       const double after = __builtin_sqrt(0.0 + eps);
-      k_cond_exp_terms<<<(int)cdivl(n_obs, 256), 256, 0, st>>>(
+      k_cond_exp_terms<<<cdiv(n_obs, 256), 256, 0, st>>>(
           n_obs, dim, B, sq_rows, batch->obs_idx, batch->n_obs_ot, 2 * weight * after,
           2 * (1 - weight), eps, terms);
     }

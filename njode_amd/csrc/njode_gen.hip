@@ -4,51 +4,20 @@
 // (njode_api.hip) routes to them every model shape the build table has no specialisation for.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
 
-#include <rocprim/rocprim.hpp>
-
-#include "../../include/njode_hip.h"
-#include "njode_error.h"
+#include "njode_call.h"
+#include "njode_env.h"
 #include "njode_gen.h"
 #include "njode_gen_seg.h"
 #include "njode_gen_host.h"
-
-namespace njode {
-void prof_mark(const char* name, hipStream_t st, bool begin);   // njode_api.hip
-}
 
 using namespace njode;
 using namespace njode::gen;
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  njode::set_error_v(code, fmt, ap);
-  va_end(ap);
-  return code;
-}
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(NJODE_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
-struct Prof {
-  const char* name;
-  hipStream_t st;
-  Prof(const char* n, hipStream_t s) : name(n), st(s) { njode::prof_mark(name, st, true); }
-  ~Prof() { njode::prof_mark(name, st, false); }
-};
-
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
 constexpr int LDS_LIMIT = 160 * 1024;
@@ -215,18 +184,14 @@ bool build_model(const NjodeDims* d, Model& m, const char** why) {
     return false;
   }
   m.nw = max_mt < 4 ? 4 : (max_mt > 16 ? 16 : max_mt);
-  if (const char* e = getenv("NJODE_GEN_NW")) {        // experiments: waves per workgroup
-    const int v = atoi(e);
-    if (v >= 1 && v <= 16) m.nw = v;
-  }
+  if (env().gen_nw >= 1 && env().gen_nw <= 16) m.nw = env().gen_nw;   // experiments: waves per workgroup
   m.S = 2048 / max_tb;
   if (m.S < 8) m.S = 8;
   if (m.S > 256) m.S = 256;
   return true;
 }
 
-struct Layout {
-  size_t total = 0;
+struct Layout : Arena {
   size_t sched, jlo, dense, bad, plan_end;
   size_t frag, loss_terms, slab, rec_ode, rec_enc, rec_dec, rec_gru = 0, ybuf, flags;
   // segment plan (unmasked loss calls): plan prefix ...
@@ -238,23 +203,7 @@ struct Layout {
   int T, PT = 16;   // path tiles and paths per tile
   int NT = 0;       // item tiles = row tiles
   bool seg = false;
-  size_t take(size_t bytes) {
-    size_t off = total;
-    total += (bytes + 255) & ~(size_t)255;
-    return off;
-  }
 };
-
-inline int bits_for(unsigned v) {  // radix bits needed for keys in [0, v]
-  int b = 1;
-  while (b < 32 && (v >> b)) ++b;
-  return b;
-}
-hipError_t sort_pairs(void* tmp, size_t& bytes, const unsigned* k_in, unsigned* k_out, const int* v_in,
-                      int* v_out, int n, int end_bit, hipStream_t st) {
-  return rocprim::radix_sort_pairs(tmp, bytes, k_in, k_out, v_in, v_out, (size_t)(n > 0 ? n : 1), 0u,
-                                   (unsigned)end_bit, st);
-}
 
 // The segment plan (njode_gen_seg.h) serves the unmasked calls that ask for the loss and not for
 // the path: training and loss-only evaluation.  NJODE_GEN_PLAN=lock keeps them on the lockstep
@@ -273,12 +222,12 @@ bool use_seg(const Model& m, int n_obs, int call_flags) {
 // for all its chains whenever ANY of its paths observes at that time, and a PhysioNet-shaped batch
 // of 50 paths is 4 tiles on a 256-CU chip: fewer paths per tile (the other chains idle) shorten
 // the serial chain of every tile -- same reasoning as q4_paths_per_tile of the specialised masked
-// kernels (njode_api.hip).  The smallest power of two that keeps the tile count within the CUs
+// kernels (njode_route.h).  The smallest power of two that keeps the tile count within the CUs
 // and the training records (one per Euler step / jump and TILE) within record_budget_bytes()
-// (njode_gen_host.h: 16 GB or 1/8 of the device's memory; round 4 allowed 40 GB).  NJODE_GEN_PT: A/B.
+// (njode_hostlib.h: 16 GB or 1/8 of the device's memory; round 4 allowed 40 GB).  NJODE_GEN_PT: A/B.
 static int gen_paths_per_tile(const Model& m, int B, int nt, int K, int call_flags) {
-  static const int env = getenv("NJODE_GEN_PT") ? atoi(getenv("NJODE_GEN_PT")) : 0;
-  if (env == 1 || env == 2 || env == 4 || env == 8 || env == 16) return env;
+  const int fixed = env().gen_pt;
+  if (fixed == 1 || fixed == 2 || fixed == 4 || fixed == 8 || fixed == 16) return fixed;
   int pt = 1;
   while (pt < 16 && (B + pt - 1) / pt > 256) pt *= 2;
   if (call_flags & NJODE_C_SAVE_BWD) {
@@ -325,8 +274,9 @@ Layout make_layout(const Model& m, int B, int n_obs, int nt, int K, int call_fla
     L.tail_order = L.take(nb * 4);
     L.tile_base = L.take(((size_t)L.NT + 1) * 4);
     size_t b0 = 0, b1 = 0;
-    (void)sort_pairs(nullptr, b0, nullptr, nullptr, nullptr, nullptr, n_obs, bits_for((unsigned)K), (hipStream_t)0);
-    (void)sort_pairs(nullptr, b1, nullptr, nullptr, nullptr, nullptr, B, bits_for((unsigned)K), (hipStream_t)0);
+    // (rocPRIM's default dispatch, never Onesweep: its temporary size is part of njode_workspace_bytes)
+    (void)sort_pairs(nullptr, b0, nullptr, nullptr, nullptr, nullptr, n_obs, bits_for((unsigned)K), false, (hipStream_t)0);
+    (void)sort_pairs(nullptr, b1, nullptr, nullptr, nullptr, nullptr, B, bits_for((unsigned)K), false, (hipStream_t)0);
     L.sort_tmp_bytes = b0 > b1 ? b0 : b1;
     L.sort_tmp = L.take(L.sort_tmp_bytes);
   }
@@ -366,15 +316,8 @@ Layout make_layout(const Model& m, int B, int n_obs, int nt, int K, int call_fla
   return L;
 }
 
+// What only this family refuses of a call check_call() (njode_call.h) has passed
 int check_sizes(const NjodeBatch* b, const NjodeSchedule* s) {
-  if (!b || !s) return fail(NJODE_E_BADARG, "null argument");
-  if (b->batch_size <= 0 || b->n_obs < 0 || s->n_steps < 0 || s->n_times < 0)
-    return fail(NJODE_E_BADARG, "negative size");
-  if (!b->start_X || (b->n_obs > 0 && (!b->X || !b->obs_idx)))
-    return fail(NJODE_E_BADARG, "null batch array");
-  if ((s->n_steps > 0 && (!s->step_dt || !s->step_t)) ||
-      (s->n_times > 0 && (!s->k_jump || !s->time_f32)) || !s->time_ptr)
-    return fail(NJODE_E_BADARG, "null schedule array");
   if ((size_t)s->n_times * (size_t)b->batch_size > ((size_t)1 << 31))
     return fail(NJODE_E_UNSUPPORTED, "n_times x batch_size exceeds 2^31 cells");
   // k_jump (host array): non-decreasing and within [0, n_steps].  The segment plan sizes its
@@ -392,25 +335,8 @@ int check_sizes(const NjodeBatch* b, const NjodeSchedule* s) {
 int build_plan(const Layout& L, char* pw, const NjodeBatch* b, const NjodeSchedule* s, hipStream_t st) {
   const int K = s->n_steps, nt = s->n_times, B = b->batch_size, n = b->n_obs;
   char* dst = pw + L.sched;
-  const size_t bdt = (size_t)K * 4, bt = (size_t)nt * 4, bp = ((size_t)nt + 1) * 4;
-  const char* h0 = (const char*)s->step_dt;
-  const bool contiguous = K > 0 && nt > 0 && (const char*)s->step_t == h0 + bdt &&
-                          (const char*)s->k_jump == h0 + 2 * bdt &&
-                          (const char*)s->time_f32 == h0 + 2 * bdt + bt &&
-                          (const char*)s->time_ptr == h0 + 2 * bdt + 2 * bt;
-  if (contiguous) {
-    HIP_TRY(hipMemcpyAsync(dst, h0, 2 * bdt + 2 * bt + bp, hipMemcpyHostToDevice, st));
-  } else {
-    if (K > 0) {
-      HIP_TRY(hipMemcpyAsync(dst, s->step_dt, bdt, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(dst + bdt, s->step_t, bdt, hipMemcpyHostToDevice, st));
-    }
-    if (nt > 0) {
-      HIP_TRY(hipMemcpyAsync(dst + 2 * bdt, s->k_jump, bt, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(dst + 2 * bdt + bt, s->time_f32, bt, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(dst + 2 * bdt + 2 * bt, s->time_ptr, bp, hipMemcpyHostToDevice, st));
-  }
+  const size_t bdt = (size_t)K * 4, bt = (size_t)nt * 4;
+  if (int rc = upload_schedule(dst, s, st)) return rc;
   const int* k_jump = (const int*)(dst + 2 * bdt);
   const int* time_ptr = (const int*)(dst + 2 * bdt + 2 * bt);
   int* dense = (int*)(pw + L.dense);
@@ -431,16 +357,15 @@ int build_plan(const Layout& L, char* pw, const NjodeBatch* b, const NjodeSchedu
         (int*)(pw + L.last_row), (unsigned*)(pw + L.tail_key), (int*)(pw + L.iota_b));
     size_t bytes = L.sort_tmp_bytes;
     HIP_TRY(sort_pairs(pw + L.sort_tmp, bytes, (const unsigned*)(pw + L.key), (unsigned*)(pw + L.key_sorted),
-                       (const int*)(pw + L.iota), (int*)(pw + L.order), n, bits_for((unsigned)K), st));
+                       (const int*)(pw + L.iota), (int*)(pw + L.order), n, bits_for((unsigned)K), false, st));
     bytes = L.sort_tmp_bytes;
     HIP_TRY(sort_pairs(pw + L.sort_tmp, bytes, (const unsigned*)(pw + L.tail_key),
                        (unsigned*)(pw + L.tail_key_sorted), (const int*)(pw + L.iota_b),
-                       (int*)(pw + L.tail_order), B, bits_for((unsigned)K), st));
+                       (int*)(pw + L.tail_order), B, bits_for((unsigned)K), false, st));
     k_gseg_tiles<<<1, 1024, 0, st>>>((const int*)(pw + L.order), (const int*)(pw + L.item_len), n, L.NT,
                                      (int*)(pw + L.tile_base));
   }
-  static const bool validate = getenv("NJODE_VALIDATE") && atoi(getenv("NJODE_VALIDATE")) != 0;
-  if (validate) {
+  if (env().validate) {
     int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, bad, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -462,14 +387,11 @@ int prepare(Call& c, const NjodeDims* dims, const float* params, const NjodeBatc
             void* ws, size_t ws_bytes) {
   const char* why;
   if (!build_model(dims, c.m, &why)) return fail(NJODE_E_UNSUPPORTED, "generic kernels: %s", why);
-  int rc = check_sizes(b, s);
+  int rc = check_call(b, s, dims->flags, call_flags, dropout_p);
+  if (!rc) rc = check_sizes(b, s);
   if (rc) return rc;
   if (!params || !ws) return fail(NJODE_E_BADARG, "null argument");
   const int B = b->batch_size, n_obs = b->n_obs, K = s->n_steps, nt = s->n_times;
-  const bool masked = (dims->flags & NJODE_F_MASKED) != 0;
-  if (masked && n_obs > 0 && !b->M) return fail(NJODE_E_BADARG, "masked model needs M");
-  if ((call_flags & NJODE_C_GET_LOSS) && !b->n_obs_ot) return fail(NJODE_E_BADARG, "get_loss needs n_obs_ot");
-  if (dropout_p < 0.0f || dropout_p >= 1.0f) return fail(NJODE_E_BADARG, "dropout_p");
   c.L = make_layout(c.m, B, n_obs, nt, K, call_flags);
   if (ws_bytes < c.L.total)
     return fail(NJODE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, c.L.total);
@@ -509,16 +431,12 @@ int prepare(Call& c, const NjodeDims* dims, const float* params, const NjodeBatc
   a.want_path = (call_flags & NJODE_C_RETURN_PATH) ? 1 : 0;
   const bool any_hidden = c.m.a.ode.nl > 1 || c.m.a.enc.nl > 1 || c.m.a.dec.nl > 1;
   a.drop = ((call_flags & NJODE_C_TRAIN) && dropout_p > 0.0f && any_hidden) ? 1 : 0;
-  unsigned thr = (unsigned)(dropout_p * 65536.0f + 0.5f);
-  if (thr > 65535u) thr = 65535u;
-  a.dc.seed_lo = (uint32_t)seed;
-  a.dc.seed_hi = (uint32_t)(seed >> 32);
-  a.dc.thr16 = a.drop ? thr : 0;
-  a.keep = 1.0f - (float)a.dc.thr16 / 65536.0f;
-  a.dc.inv_keep = 1.0f / a.keep;
+  const DropSetup ds = make_drop_ctx(dropout_p, seed, a.drop != 0);
+  a.dc = ds.dc;
+  a.keep = ds.keep;
   a.weight = weight;
 #ifdef NJ_GEN_ABL
-  a.dbg = getenv("NJODE_GEN_DBG") ? atoi(getenv("NJODE_GEN_DBG")) : 0;
+  a.dbg = env().gen_dbg;
 #endif
   memset(&c.g, 0, sizeof(c.g));
   if (c.L.seg) {
@@ -528,23 +446,8 @@ int prepare(Call& c, const NjodeDims* dims, const float* params, const NjodeBatc
     // tiles per CU and pay the per-wave, per-layer scalar work a quarter as often
     // (profiles/r03_generic_waves_per_tile.txt: width 100, 20 000 paths: 8.0 -> 5.8 ms).
     // (per device: a process may drive GPUs of different sizes)
-    static std::mutex cu_mu;
-    static int cu_of_dev[64] = {};
-    int n_cu = 256;
-    {
-      int dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        std::lock_guard<std::mutex> lk(cu_mu);
-        if (cu_of_dev[dev] <= 0) {
-          int v = 0;
-          if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-          cu_of_dev[dev] = v;
-        }
-        n_cu = cu_of_dev[dev];
-      }
-    }
-    if (!getenv("NJODE_GEN_NW") && c.m.nw > 4 && (long long)c.L.NT >= 16LL * n_cu) c.m.nw = 4;
+    const int n_cu = device_cu_count();
+    if (env().gen_nw == -1 && c.m.nw > 4 && (long long)c.L.NT >= 16LL * n_cu) c.m.nw = 4;
   }
   {
     // output tiles per wave, now that the waves per workgroup are known
@@ -627,7 +530,8 @@ int gen_plan(const NjodeDims* dims, const NjodeBatch* b, const NjodeSchedule* s,
   Model m;
   const char* why;
   if (!build_model(dims, m, &why)) return fail(NJODE_E_UNSUPPORTED, "generic kernels: %s", why);
-  int rc = check_sizes(b, s);
+  int rc = check_call(b, s, 0, 0, 0.0f);   // (a plan reads neither M nor n_obs_ot)
+  if (!rc) rc = check_sizes(b, s);
   if (rc) return rc;
   if (!plan) return fail(NJODE_E_BADARG, "null plan buffer");
   const Layout L = make_layout(m, b->batch_size, b->n_obs, s->n_times, s->n_steps, call_flags);
@@ -652,7 +556,7 @@ int gen_forward(const NjodeDims* dims, const float* params, const NjodeBatch* b,
     if ((rc = build_plan(c.L, (char*)ws, b, s, st))) return rc;
   }
   {
-    Prof ps("k_gen_pack", st);
+    ProfScope ps("k_gen_pack", st);
     k_gen_pack<<<cdiv(c.m.pack.total, 256), 256, 0, st>>>(params, (float*)c.a.frag, c.m.pack);
   }
   if (c.L.seg) {
@@ -662,15 +566,15 @@ int gen_forward(const NjodeDims* dims, const float* params, const NjodeBatch* b,
         (rc = set_lds((const void*)k_gseg_mid, lds)))
       return rc;
     {
-      Prof ps("k_gseg_enc", st);
+      ProfScope ps("k_gseg_enc", st);
       k_gseg_enc<<<c.g.NT + c.g.TB, nth, lds, st>>>(c.a, c.g);
     }
     {
-      Prof ps("k_gseg_ode_fwd", st);
+      ProfScope ps("k_gseg_ode_fwd", st);
       k_gseg_ode_fwd<<<c.g.NT + (c.g.tails ? c.g.TB : 0), nth, lds, st>>>(c.a, c.g);
     }
     {
-      Prof ps("k_gseg_mid", st);
+      ProfScope ps("k_gseg_mid", st);
       k_gseg_mid<<<c.g.NT, nth, lds, st>>>(c.a, c.g);
     }
     k_gen_sum<<<1, 1024, 0, st>>>(c.a.loss_terms, b->n_obs, loss);
@@ -680,7 +584,7 @@ int gen_forward(const NjodeDims* dims, const float* params, const NjodeBatch* b,
   if (c.a.save) HIP_TRY(hipMemsetAsync(c.a.flags, 0, (size_t)(s->n_times > 0 ? s->n_times : 1) * c.L.T * 4, st));
   if ((rc = set_lds((const void*)k_gen_fwd, c.m.lds_bytes))) return rc;
   {
-    Prof ps("k_gen_fwd", st);
+    ProfScope ps("k_gen_fwd", st);
     k_gen_fwd<<<c.L.T, c.m.nw * 64, c.m.lds_bytes, st>>>(c.a);
   }
   if (want_loss) k_gen_sum<<<1, 1024, 0, st>>>(c.a.loss_terms, b->batch_size, loss);
@@ -708,16 +612,16 @@ int gen_backward(const NjodeDims* dims, const float* params, const NjodeBatch* b
     if ((rc = set_lds((const void*)k_gseg_ode_bwd, lds)) || (rc = set_lds((const void*)k_gseg_enc_bwd, lds)))
       return rc;
     {
-      Prof ps("k_gseg_ode_bwd", st);
+      ProfScope ps("k_gseg_ode_bwd", st);
       k_gseg_ode_bwd<<<c.g.NT, nth, lds, st>>>(c.a, c.g);
     }
     {
-      Prof ps("k_gseg_enc_bwd", st);
+      ProfScope ps("k_gseg_enc_bwd", st);
       k_gseg_enc_bwd<<<c.g.NT + c.g.TB, nth, lds, st>>>(c.a, c.g);
     }
   } else {
     if ((rc = set_lds((const void*)k_gen_bwd, c.m.lds_bytes))) return rc;
-    Prof ps("k_gen_bwd", st);
+    ProfScope ps("k_gen_bwd", st);
     k_gen_bwd<<<c.L.T, c.m.nw * 64, c.m.lds_bytes, st>>>(c.a);
   }
   float* slab = (float*)((char*)ws + c.L.slab);
@@ -752,14 +656,14 @@ int gen_backward(const NjodeDims* dims, const float* params, const NjodeBatch* b
     }
   };
   if (c.L.seg) {
-    Prof ps("k_gen_dw", st);
+    ProfScope ps("k_gen_dw", st);
     n_rec_dev = c.g.tile_base + c.g.NT;        // the number of ODE records is known on the device only
     dw(a.ode, a.rec_ode, (long long)a.K * (T + 1) + 1, nullptr, 1, 0);
     n_rec_dev = nullptr;
     dw(a.enc, a.rec_enc, (long long)c.g.NT + c.g.TB, nullptr, 1, 0);
     dw(a.dec, a.rec_dec, (long long)c.g.NT * 2, nullptr, 1, 0);
   } else {
-    Prof ps("k_gen_dw", st);
+    ProfScope ps("k_gen_dw", st);
     dw(a.ode, a.rec_ode, (long long)a.K * T, nullptr, 1, 0);
     if (a.rnn) {
       // (the encoder only produced the start states; the jumps went through the GRU cell)

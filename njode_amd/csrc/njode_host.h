@@ -7,16 +7,12 @@
 #include "njode_mfma_lockstep.h"
 #include "njode_mfma_split.h"
 #include "njode_mfma_lock4.h"
+#include "njode_env.h"
+#include "njode_hostlib.h"
 
 namespace njode {
 
 constexpr int MAX_WAVES = 2048;
-// ODE-evolve implementations: matrix cores (default where compiled), VALU with weights
-// through the scalar cache
-constexpr int ODE_MFMA = 0, ODE_VALU = 1;
-// (NJODE_ODE=mfma1 keeps ODE_MFMA but with one wave per tile, njode_mfma.h, where the default
-// picks the mixed kernels of njode_mfma_split.h: A/B baseline)
-
 struct Route;   // njode_route.h: what a call runs, decided once; the launchers switch on it
 
 struct CfgOps {
@@ -58,16 +54,6 @@ struct SideInfo {
   hipStream_t st2;
   hipEvent_t e2;
   int tails_sorted_on_st2;   // the plan's tail order was enqueued on st2 (else on the caller's stream)
-};
-
-// Optional per-kernel timing (njode_profile_enable / njode_profile_read): HIP events
-// recorded on the launch stream around each kernel.  Defined in njode_api.hip.
-void prof_mark(const char* name, hipStream_t st, bool begin);
-struct ProfScope {
-  const char* name;
-  hipStream_t st;
-  ProfScope(const char* n, hipStream_t s) : name(n), st(s) { prof_mark(name, st, true); }
-  ~ProfScope() { prof_mark(name, st, false); }
 };
 
 }  // namespace njode

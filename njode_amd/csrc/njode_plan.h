@@ -11,9 +11,9 @@
 // THE ODE FORWARD'S LAUNCH of the current step (k_ode_fwd_mixed, njode_mfma_split.h): same queue, no
 // events, no dispatches of its own, beside a kernel that is long enough to cover it.  The stages are
 // separated by grid barriers among the P plan blocks (all of them resident from the start: they hold the
-// lowest block indices; P = rows / 4096 + 1 <= 64 when hosted, at most 256 = one per CU: njode_api.hip);
+// lowest block indices; P = rows / 4096 + 1 <= 64 when hosted, at most 256 = one per CU: njode_planner.hip);
 // P = 1 needs workgroup barriers only.  The same body is also a kernel of its own (k_plan_grid,
-// njode_api.hip) for calls that build their plan in line -- whole for small plans, from its third stage
+// njode_planner.hip) for calls that build their plan in line -- whole for small plans, from its third stage
 // on (first_stage = 2) behind k_row_time for large ones.
 //
 // Same arrays, bit for bit, as the multi-launch plan: the order is a stable counting sort whatever

@@ -6,29 +6,15 @@
 // per grid time ranks the batch's observations with a ballot scan.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 
 #include "../../include/njode_producer.h"
-#include "njode_error.h"
+#include "njode_hostlib.h"
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  njode::set_error_v(code, fmt, ap);
-  va_end(ap);
-  return code;
-}
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(NJODE_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
+using namespace njode;
 
-inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
 
 // ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
 // 1, 2, 3", SC'11) ---------------------------------------------------------------------

@@ -14,40 +14,15 @@
 // float atomics), so two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 
 #include "../../include/njode_protocol.h"
-#include "njode_error.h"
-
-namespace njode {
-void prof_mark(const char* name, hipStream_t st, bool begin);   // njode_api.hip
-}
+#include "njode_hostlib.h"
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  njode::set_error_v(code, fmt, ap);
-  va_end(ap);
-  return code;
-}
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(NJODE_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
+using namespace njode;
 
-struct Prof {
-  const char* name;
-  hipStream_t st;
-  Prof(const char* n, hipStream_t s) : name(n), st(s) { njode::prof_mark(name, st, true); }
-  ~Prof() { njode::prof_mark(name, st, false); }
-};
-
-inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
 inline long long minl(long long a, long long b) { return a < b ? a : b; }
 inline long long maxl(long long a, long long b) { return a > b ? a : b; }
 inline size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
@@ -68,10 +43,10 @@ DensePlan dense_plan(long long T2, long long B, long long dim) {
   DensePlan p;
   p.A = (int)minl(dim, WB);
   p.G = WB / p.A;
-  const long long most = cdivl(T2, p.G);                       // a chunk is at least one stride
-  const long long nc = maxl(1, minl(most, cdivl(SLOTS_AIM, B)));
-  p.chunk_len = (int)(cdivl(cdivl(T2, nc), p.G) * p.G);
-  p.n_chunks = T2 > 0 ? (int)cdivl(T2, p.chunk_len) : 0;
+  const long long most = cdiv(T2, p.G);                       // a chunk is at least one stride
+  const long long nc = maxl(1, minl(most, cdiv(SLOTS_AIM, B)));
+  p.chunk_len = (int)(cdiv(cdiv(T2, nc), p.G) * p.G);
+  p.n_chunks = T2 > 0 ? cdiv(T2, p.chunk_len) : 0;
   return p;
 }
 
@@ -83,8 +58,8 @@ struct Layout {
 Layout layout(long long n_query, long long B, long long dim) {
   // B * n_chunks <= min(B + SLOTS_AIM, B * max(1, ceil(T2 / G))): both non-decreasing in T2, B, dim
   const long long G = WB / minl(dim, WB);
-  const long long slots = minl(B + SLOTS_AIM, B * maxl(1, cdivl(n_query, G)));
-  const long long sparse = minl(cdivl(n_query * dim, WB), SPARSE_WG);
+  const long long slots = minl(B + SLOTS_AIM, B * maxl(1, cdiv(n_query, G)));
+  const long long sparse = minl(cdiv(n_query * dim, WB), SPARSE_WG);
   Layout L;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += pad256(bytes); return at; };
@@ -359,7 +334,7 @@ extern "C" int njode_protocol_rows(const double* path_t, int32_t n_rows, const d
     return fail(NJODE_E_BADARG, "unknown row rule %d", rule);
   if (n_query == 0) return NJODE_OK;
   hipStream_t st = (hipStream_t)stream;
-  k_protocol_rows<<<(int)cdivl(n_query, 256), 256, 0, st>>>(path_t, n_rows, query, n_query, rule, rows);
+  k_protocol_rows<<<cdiv(n_query, 256), 256, 0, st>>>(path_t, n_rows, query, n_query, rule, rows);
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
 }
@@ -393,15 +368,15 @@ extern "C" int njode_protocol_score_f32(const NjodeProtocolJob* job, double* out
     int* attr_cnt = (int*)(w + L.attr_cnt);
     n_part = (long long)B * pl.n_chunks;
     if (n_part > 0) {
-      Prof ps("k_protocol_dense", st);
+      ProfScope ps("k_protocol_dense", st);
       k_protocol_dense<<<(int)n_part, WB, 0, st>>>(job->pred, job->rows, job->vals, job->mask,
                                                    job->n_rows, B, dim, nq, pl, part, attr_se, attr_cnt);
     }
     k_protocol_attr<<<B, WB, 0, st>>>(dim, pl.n_chunks, attr_se, attr_cnt, path_mean);
   } else {
-    n_part = minl(cdivl((long long)nq * dim, WB), SPARSE_WG);
+    n_part = minl(cdiv((long long)nq * dim, WB), SPARSE_WG);
     if (n_part > 0) {
-      Prof ps("k_protocol_sparse", st);
+      ProfScope ps("k_protocol_sparse", st);
       k_protocol_sparse<<<(int)n_part, WB, 0, st>>>(job->pred, job->rows, job->X_val, job->M_val,
                                                     job->index_val, job->n_rows, B, dim, nq, part);
     }
