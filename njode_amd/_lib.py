@@ -8,6 +8,8 @@ module's ``lib()`` raises, and every product entry point goes through it.
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (NJODE_LIB: another build of the same library, e.g. the diagnostic build of tools/ubench)
 LIB_PATH = os.environ.get('NJODE_LIB') or os.path.join(_HERE, 'libnjode_hip.so')
@@ -222,6 +224,16 @@ def lib():
     L.njode_debug_plan_stamps.argtypes = [vp, C.c_int]
     _lib = L
     return L
+
+
+def stream_arg(device):
+    """torch's current stream on ``device`` as a ``hipStream_t`` argument."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr_arg(t):
+    """A tensor's address (None: the null pointer) as a pointer argument."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def check(rc):

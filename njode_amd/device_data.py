@@ -17,17 +17,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr_arg as _ptr, stream_arg as _stream
 from .schedule import PinnedRing, cond_exp_clock
 
 _HP_KEYS = ('drift', 'volatility', 'mean', 'speed', 'correlation', 'S0', 'maturity')
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def parse_powers(func_names):

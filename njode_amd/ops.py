@@ -5,7 +5,7 @@ via PyTorch-ROCm custom ops"): ``torch.ops.njode_amd.forward`` is one dispatcher
 implementation and a registered autograd formula that calls ``njode_backward_f32``.
 
 The model class uses it when constructed with ``options={'torch_library_op': True}``; the
-default route is the ``torch.autograd.Function`` of ``models.py`` (same two library calls).
+default route is the ``torch.autograd.Function`` of ``_calls.py`` (same two library calls).
 Both routes produce the same numbers (``tests/test_hip_torch_op.py``).
 
 Operator schema::
@@ -50,14 +50,14 @@ def forward(params: List[Tensor], start_X: Tensor, X: Tensor, obs_idx: Tensor,
             delta_t: float, T: float, model_id: int, get_loss: bool, until_T: bool,
             save_bwd: bool) -> Tuple[Tensor, Tensor, Tensor]:
     model = _MODELS[model_id]
-    call, sched, slot_i, B = model._make_call(
-        times.numpy(), time_ptr.numpy(), X, obs_idx, delta_t, T, start_X, n_obs_ot, False,
-        get_loss, until_T, M, save_bwd=save_bwd)
+    call = model._arm_call(model._describe_call(
+        times.numpy(), time_ptr.numpy(), X, obs_idx, delta_t, T, start_X, n_obs_ot,
+        get_loss=get_loss, until_T=until_T, M=M, save_bwd=save_bwd))
     dev = start_X.device
-    hT = torch.empty(B, model.hidden_size, dtype=torch.float32, device=dev)
+    hT = torch.empty(call.sizes[0], model.hidden_size, dtype=torch.float32, device=dev)
     loss = torch.zeros(1, dtype=torch.float32, device=dev)
     try:
-        model._run_forward(call, hT, loss if get_loss else None, None, None, slot_i)
+        model._run_forward(call, hT, loss if get_loss else None)
     except Exception:
         model._release_ws(call)
         raise
@@ -85,9 +85,8 @@ def _drop_call(call_id):
     without a backward, e.g. a validation loss computed without no_grad): release the saved
     call, which returns its workspace to the model's pool."""
     call = _CALLS.pop(call_id, None)
-    if call is not None and call.ws_slot is not None:
-        call.ws_slot[1] = False
-        call.ws_slot = None
+    if call is not None:
+        call.release()
 
 
 def _setup_context(ctx, inputs, output):
@@ -95,13 +94,13 @@ def _setup_context(ctx, inputs, output):
     ctx.n_params = len(inputs[0])
     ctx.call_id = int(output[2])
     ctx.set_materialize_grads(False)     # an unused output's gradient arrives as None, not zeros
-    ctx.save_for_backward(*inputs[0])    # (their version counters: models._check_saved)
+    ctx.save_for_backward(*inputs[0])    # (their version counters: _calls._check_saved)
     if ctx.call_id:
         weakref.finalize(ctx, _drop_call, ctx.call_id)
 
 
 def _backward(ctx, grad_hT, grad_loss, grad_id):
-    from .models import _check_saved, _hT_and_loss_grads
+    from ._calls import _check_saved, _hT_and_loss_grads
     model = _MODELS[ctx.model_id]
     call = _CALLS.pop(ctx.call_id, None)
     if call is None:
@@ -110,8 +109,7 @@ def _backward(ctx, grad_hT, grad_loss, grad_id):
     _check_saved(ctx, model, call)
     # (round 4 received grad_hT here and dropped it; now the hT term is differentiated too)
     grad_flat = _hT_and_loss_grads(model, call, grad_loss, grad_hT)
-    grads = [grad_flat[off:off + n].view(shape) for (off, n, shape) in model._param_slices]
-    return (grads,) + (None,) * 13
+    return (model._split_flat(grad_flat),) + (None,) * 13
 
 
 torch.library.register_autograd('njode_amd::forward', _backward, setup_context=_setup_context)

@@ -15,12 +15,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import stream_arg as _stream
 
 RULES = {'closest': _lib.ROWS_CLOSEST, 'first_nearest': _lib.ROWS_FIRST_NEAREST}
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _need_cuda(**tensors):

@@ -30,7 +30,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device_data import _host_rows, _ptr, _stream
+from ._lib import ptr_arg as _ptr, stream_arg as _stream
+from .device_data import _host_rows
 
 LAYOUTS = ('train', 'test')
 

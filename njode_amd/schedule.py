@@ -20,6 +20,7 @@ import collections
 import numpy as np
 import torch
 
+from . import _lib
 
 def _walk_clock(times, delta_t, T, until_T, strict=False):
     """The float64 clock of one pass: (step lengths, clock before each step, k_jump, path_t,
@@ -91,6 +92,12 @@ class Schedule:
         f[2 * K + nt:2 * K + 2 * nt] = self.time_f32
         buf[2 * K + 2 * nt:2 * K + 3 * nt + 1] = time_ptr
         return K, nt
+
+    def struct(self, base):
+        """The ``NjodeSchedule`` over a buffer ``pack_into`` has filled, at address ``base``."""
+        K, nt = self.n_steps, self.n_times
+        return _lib.NjodeSchedule(K, nt, base, base + 4 * K, base + 8 * K, base + 8 * K + 4 * nt,
+                                  base + 8 * K + 8 * nt)
 
 
 CondExpClock = collections.namedtuple(

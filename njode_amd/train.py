@@ -25,14 +25,13 @@ The fused step (``NJODE.loss_and_grad`` + ``FusedAdam``) is used by default; pas
 (``loss.backward()`` + ``torch.optim.Adam``).  With torch.distributed initialised the
 loop is data parallel (see ``parallel.py``).
 """
-import csv
-import os
 import time
 
 import numpy as np
 import torch
 
-from . import data_utils, device_data, models, parallel, stock_model
+from . import data_utils, device_data, parallel, stock_model
+from .run import Run, new_model_and_optimizer, plan_ahead_on, wants_prefetch
 
 METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss',
                 'optimal_eval_loss']
@@ -95,21 +94,10 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
     mult = len(funcs) + 1
 
     train_idx, val_idx = split_indices(len(nb_obs), test_size, seed)
-    model_opts = dict(options)
-    model_opts['device_outputs'] = True
-    torch.manual_seed(0)
-    model = models.NJODE(input_size * mult, hidden_size, output_size * mult, ode_nn,
-                         readout_nn, enc_nn, use_rnn, bias=bias, dropout_rate=dropout_rate,
-                         solver=solver, weight=weight, weight_decay=weight_decay,
-                         options=model_opts).to(device)
-    if init_state is not None:     # start from given weights (like-for-like runs against the reference)
-        model.load_state_dict(init_state)
-    parallel.broadcast_parameters_(model.flat_parameters())
-    if fused:
-        optimizer = models.FusedAdam(model, lr=learning_rate, weight_decay=0.0005,
-                                     distributed=world > 1)
-    else:
-        optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate, weight_decay=0.0005)
+    model, optimizer = new_model_and_optimizer(
+        (input_size * mult, hidden_size, output_size * mult), (ode_nn, readout_nn, enc_nn), use_rnn,
+        device, options, fused, learning_rate, init_state, world, bias=bias,
+        dropout_rate=dropout_rate, solver=solver, weight=weight, weight_decay=weight_decay)
 
     val = data_utils.collate_arrays(stock_paths[val_idx], observed_dates[val_idx],
                                     nb_obs[val_idx], delta_t, funcs)
@@ -129,35 +117,11 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
 
     dev_ds = device_data.DeviceDataset.from_arrays(stock_paths, observed_dates, nb_obs, metadata,
                                                    device) if device_collate else None
-    # checkpoints and the metric file (reference train.py:344-350, 400-418)
-    columns = METR_COLUMNS + (['evaluation_mean_diff'] if evaluate else [])
-    best_eval_loss = np.inf
-    path_last = path_best = metric_file = None
-    saved_rows = []
-    if model_path is not None:
-        model_dir = os.path.join(model_path, 'id-{}'.format(model_id))
-        path_last = os.path.join(model_dir, 'last_checkpoint')
-        path_best = os.path.join(model_dir, 'best_checkpoint')
-        metric_file = os.path.join(model_dir, 'metric_id-{}.csv'.format(model_id))
-        os.makedirs(model_dir, exist_ok=True)
-        if resume_training and os.path.exists(os.path.join(
-                path_best if load_best else path_last, 'checkpt.tar')):
-            models.get_ckpt_model(path_best if load_best else path_last, model, optimizer, device)
-            if os.path.exists(metric_file):
-                with open(metric_file) as f:
-                    saved_rows = [[float(x) for x in r[1:]] for r in list(csv.reader(f))[1:]]
-                if saved_rows:
-                    best_eval_loss = min(r[4] for r in saved_rows)
-            model.epoch += 1
-            model.weight_decay_step()
-
-    def write_metrics():
-        # pandas' DataFrame.to_csv layout: unnamed index column first
-        with open(metric_file, 'w', newline='') as f:
-            wr = csv.writer(f)
-            wr.writerow([''] + columns)
-            for i, r in enumerate(saved_rows):
-                wr.writerow([i] + r)
+    # checkpoints and the metric file (reference train.py:344-350, 400-418): the best checkpoint
+    # follows eval_loss, and an improvement also writes last_checkpoint; rank 0 writes
+    run = Run(model_path, model_id, METR_COLUMNS + (['evaluation_mean_diff'] if evaluate else []), log,
+              best_col=4, save_on_best=True, writes=rank == 0)
+    run.resume(model, optimizer, device, resume_training, load_best)
 
     def plan_epoch(epoch):
         """Shuffled order of an epoch and (device collate) phase 1 of the collate for ALL of its
@@ -184,7 +148,6 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
         return order, n_steps, prepared
 
     metrics = []
-    pending = []
     epoch_plan = {}
     while model.epoch <= epochs:
         t0 = time.time()
@@ -208,25 +171,16 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
                 d = _device_batch(b, device)
             return idx, lo, mine, d
 
-        # (NJODE_PLAN_AHEAD=0: A/B switch for the look-ahead)
-        plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
+        plan_ahead = plan_ahead_on(plan_ahead)
         nxt = prepare(0) if n_steps > 0 else None
         for s in range(n_steps):
             idx, lo, mine, d = nxt
             # one batch ahead: the next batch is collated now, and (fused loop) its execution
             # plan is built on a helper stream beside this step (NJODE.prefetch_plan)
             nxt = prepare(s + 1) if s + 1 < n_steps else None
-            # Where it pays (profiles/r03_harness_epochs.jsonl, epoch paths/s with / without):
-            # B = 100: 316 k / 297 k, B = 200: 572 k / 524 k -- the step is a chain of ~5 us
-            # launches and the plan's six are off it; B = 1 000: 1.83 M / 2.04 M -- the plan
-            # kernels queued ahead delay the step's own; B >= 4 096: the plan (~0.1 ms) hides
-            # beside the ODE kernels (bench.py: 1.19 -> 1.14 ms at 20 000 paths).
             n_next = len(nxt[2]) if nxt is not None else 0
-            # (round 5: up to ~260 000 rows the plan rides inside this step's ODE-forward launch --
-            # no helper stream, it pays at every size: NJODE.plan_defer_ok)
-            if plan_ahead and fused and n_next >= max(plan_ahead_min, 1) and \
-                    (n_next <= 512 or n_next >= 4096 or
-                     model.plan_defer_ok(int(nxt[3]['time_ptr'][-1]))):
+            if plan_ahead and fused and n_next and wants_prefetch(
+                    model, n_next, int(nxt[3]['time_ptr'][-1]), plan_ahead_min):
                 dn = nxt[3]
                 model.prefetch_plan(dn['times'], dn['time_ptr'], dn['X'], dn['obs_idx'], delta_t, T,
                                     dn['start_X'], dn['n_obs_ot'], need_hT=False)
@@ -294,19 +248,8 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
                                             opt_eval_loss, loss_val))
         row = [model.epoch, train_time, eval_time, train_loss, loss_val, opt_eval_loss] + row_extra
         metrics.append(row)
-        pending.append(row)
-        if model_path is not None and rank == 0:
-            improved = loss_val < best_eval_loss
-            if model.epoch % save_every == 0 or improved:
-                saved_rows.extend(pending)
-                pending = []
-                write_metrics()
-                models.save_checkpoint(model, optimizer, path_last, model.epoch)
-            if improved:
-                log('save new best model: last-best-loss: {:.5f}, new-best-loss: {:.5f}, '
-                    'epoch: {}'.format(best_eval_loss, loss_val, model.epoch))
-                models.save_checkpoint(model, optimizer, path_best, model.epoch)
-                best_eval_loss = loss_val
+        run.end_of_epoch(model, optimizer, row, save_every)
+        run.new_best(model, optimizer, loss_val)
         model.epoch += 1
         model.weight_decay_step()
     return model, metrics

@@ -23,14 +23,13 @@ the reference (``loss.backward()`` + ``torch.optim.Adam``).  Single process only
 ``NJODE/climate_train.py:356-488``: a validation and a test set, each one batch in the climate
 validation layout, scored after every epoch (``climate_eval.evaluate_model_device``).
 """
-import csv
-import os
 import time
 
 import numpy as np
 import torch
 
-from . import climate_eval, models, parallel, physionet_eval, synthetic_physionet
+from . import climate_eval, parallel, physionet_eval, synthetic_physionet
+from .run import Run, new_model_and_optimizer, plan_ahead_on, require_single_process, wants_prefetch
 
 METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss', 'eval_metric',
                 'eval_metric_2']
@@ -63,9 +62,8 @@ def _epoch_steps(model, optimizer, dataset, lists, prepared, dev, delta_t, T, fu
     for s in range(len(lists)):
         d = nxt
         nxt = prepare(s + 1) if s + 1 < len(lists) else None
-        # (the conditions of train.train; a masked model never defers its plan)
-        if plan_ahead and fused and nxt is not None and \
-                (nxt['batch_size'] <= 512 or nxt['batch_size'] >= 4096):
+        if plan_ahead and fused and nxt is not None and wants_prefetch(
+                model, nxt['batch_size'], int(nxt['time_ptr'][-1])):
             model.prefetch_plan(nxt['times'], nxt['time_ptr'], nxt['X'], nxt['obs_idx'], delta_t,
                                 T, nxt['start_X'], nxt['n_obs_ot'], M=nxt['M'], need_hT=True)
         args = (d['times'], d['time_ptr'], d['X'], d['obs_idx'], delta_t, T, d['start_X'],
@@ -78,65 +76,6 @@ def _epoch_steps(model, optimizer, dataset, lists, prepared, dev, delta_t, T, fu
             loss.backward()
         optimizer.step()
     return loss
-
-
-class _Run:
-    """Checkpoints, metric file and resume of one model id under ``model_path`` (None: nothing is
-    written) -- what the two loops below share.  ``columns[5]`` is the ``eval_metric`` the best
-    checkpoint follows."""
-
-    def __init__(self, model_path, model_id, columns, log):
-        self.columns, self.log = columns, log
-        self.best_eval_metric = np.inf
-        self.path_last = self.path_best = self.metric_file = None
-        self.saved_rows, self.pending = [], []
-        if model_path is not None:
-            model_dir = os.path.join(model_path, 'id-{}'.format(model_id))
-            self.path_last = os.path.join(model_dir, 'last_checkpoint')
-            self.path_best = os.path.join(model_dir, 'best_checkpoint')
-            self.metric_file = os.path.join(model_dir, 'metric_id-{}.csv'.format(model_id))
-            os.makedirs(model_dir, exist_ok=True)
-
-    def resume(self, model, optimizer, dev, resume_training, load_best):
-        if self.metric_file is None or not resume_training:
-            return
-        path = self.path_best if load_best else self.path_last
-        if not os.path.exists(os.path.join(path, 'checkpt.tar')):
-            return
-        models.get_ckpt_model(path, model, optimizer, dev)
-        if os.path.exists(self.metric_file):
-            with open(self.metric_file) as f:
-                self.saved_rows = [[float(x) for x in r[1:]] for r in list(csv.reader(f))[1:]]
-            if self.saved_rows:
-                self.best_eval_metric = min(r[5] for r in self.saved_rows)
-        model.epoch += 1
-        model.weight_decay_step()
-
-    def write_metrics(self):
-        # pandas' DataFrame.to_csv layout: unnamed index column first
-        with open(self.metric_file, 'w', newline='') as f:
-            wr = csv.writer(f)
-            wr.writerow([''] + self.columns)
-            for i, r in enumerate(self.saved_rows):
-                wr.writerow([i] + r)
-
-    def new_best(self, model, optimizer, mse_val):
-        """``best_checkpoint`` when ``eval_metric`` improves."""
-        if self.metric_file is None or not mse_val < self.best_eval_metric:
-            return
-        self.log('save new best model: last-best-metric: {:.5f}, new-best-metric: {:.5f}, '
-                 'epoch: {}'.format(self.best_eval_metric, mse_val, model.epoch))
-        models.save_checkpoint(model, optimizer, self.path_best, model.epoch)
-        self.best_eval_metric = mse_val
-
-    def end_of_epoch(self, model, optimizer, row, save_every):
-        """The epoch's metric row; ``last_checkpoint`` + metric file every ``save_every`` epochs."""
-        self.pending.append(row)
-        if self.metric_file is not None and model.epoch % save_every == 0:
-            self.saved_rows.extend(self.pending)
-            self.pending = []
-            self.write_metrics()
-            models.save_checkpoint(model, optimizer, self.path_last, model.epoch)
 
 
 def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learning_rate=1e-3,
@@ -156,9 +95,7 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
     ``train.train`` applies; the test batches, held-out arrays included, are built once and stay in
     HBM.  ``device_collate=False`` collates on the host (``collate_host``) and uploads: the same
     batches, bit for bit.  ``ValueError`` under a process group of more than one rank."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() \
-            and torch.distributed.get_world_size() > 1:
-        raise ValueError('train_records is single process: multi-GPU record training is not offered')
+    require_single_process('train_records')
     train_idx = np.asarray(train_idx, dtype=np.int64).reshape(-1)
     test_idx = np.asarray(test_idx, dtype=np.int64).reshape(-1)
     if len(train_idx) == 0 or len(test_idx) == 0 or batch_size <= 0:
@@ -166,20 +103,10 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
     if device_collate and dataset.device is None:
         raise ValueError('device_collate needs a RecordDataset resident on the GPU')
     dev = torch.device(device)
-    model_opts = dict(options)
-    model_opts['masked'] = True
-    model_opts['device_outputs'] = True
-    dim = dataset.dim
-    torch.manual_seed(0)
-    model = models.NJODE(dim, hidden_size, dim, ode_nn, readout_nn, enc_nn, use_rnn, bias=bias,
-                         dropout_rate=dropout_rate, solver=solver, weight=weight,
-                         weight_decay=weight_decay, options=model_opts).to(dev)
-    if init_state is not None:
-        model.load_state_dict(init_state)
-    if fused:
-        optimizer = models.FusedAdam(model, lr=learning_rate, weight_decay=0.0005)
-    else:
-        optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate, weight_decay=0.0005)
+    model, optimizer = new_model_and_optimizer(
+        (dataset.dim, hidden_size, dataset.dim), (ode_nn, readout_nn, enc_nn), use_rnn, dev,
+        dict(options, masked=True), fused, learning_rate, init_state, bias=bias,
+        dropout_rate=dropout_rate, solver=solver, weight=weight, weight_decay=weight_decay)
 
     # the test batches never change: collated once, in the records' order
     test_lists = [test_idx[i:i + batch_size] for i in range(0, len(test_idx), batch_size)]
@@ -188,7 +115,7 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
     else:
         test_batches = [_upload(dataset.collate_host(ix, 'test'), dev) for ix in test_lists]
 
-    run = _Run(model_path, model_id, METR_COLUMNS, log)
+    run = Run(model_path, model_id, METR_COLUMNS, log, best_col=5, save_on_best=False)
     run.resume(model, optimizer, dev, resume_training, load_best)
 
     def plan_epoch(epoch):
@@ -196,7 +123,7 @@ def train_records(dataset, train_idx, test_idx, epochs=1, batch_size=50, learnin
         lists = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
         return lists, dataset.prepare_batches(lists, 'train') if device_collate else None
 
-    plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
+    plan_ahead = plan_ahead_on(plan_ahead)
     metrics, epoch_plan = [], {}
     while model.epoch <= epochs:
         t0 = time.time()
@@ -252,10 +179,7 @@ def train_climate_records(dataset, train_idx, val_idx, test_idx, epochs=1, batch
     ``device_collate``, ``fused``, ``resume_training`` / ``load_best`` as in ``train_records``.
     ``ValueError`` for an empty eligible validation or test set and under a process group of more
     than one rank."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() \
-            and torch.distributed.get_world_size() > 1:
-        raise ValueError('train_climate_records is single process: multi-GPU record training is '
-                         'not offered')
+    require_single_process('train_climate_records')
     train_idx = np.asarray(train_idx, dtype=np.int64).reshape(-1)
     if len(train_idx) == 0 or batch_size <= 0:
         raise ValueError('train_idx and batch_size must not be empty')
@@ -266,21 +190,12 @@ def train_climate_records(dataset, train_idx, val_idx, test_idx, epochs=1, batch
         raise ValueError('no record of the validation or of the test set has a row up to T_val = '
                          '{} and a row after it'.format(T_val))
     dev = torch.device(device)
-    model_opts = dict(options)
+    model_opts = dict(options, masked=True)
     delta_t = model_opts.pop('delta_t', climate_eval.CLIMATE_DELTA_T)
-    model_opts['masked'] = True
-    model_opts['device_outputs'] = True
-    dim = dataset.dim
-    torch.manual_seed(0)
-    model = models.NJODE(dim, hidden_size, dim, ode_nn, readout_nn, enc_nn, use_rnn, bias=bias,
-                         dropout_rate=dropout_rate, solver=solver, weight=weight,
-                         weight_decay=weight_decay, options=model_opts).to(dev)
-    if init_state is not None:
-        model.load_state_dict(init_state)
-    if fused:
-        optimizer = models.FusedAdam(model, lr=learning_rate, weight_decay=0.0005)
-    else:
-        optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate, weight_decay=0.0005)
+    model, optimizer = new_model_and_optimizer(
+        (dataset.dim, hidden_size, dataset.dim), (ode_nn, readout_nn, enc_nn), use_rnn, dev,
+        model_opts, fused, learning_rate, init_state, bias=bias, dropout_rate=dropout_rate,
+        solver=solver, weight=weight, weight_decay=weight_decay)
 
     # the validation and the test set never change: one batch each, collated once
     if device_collate:
@@ -290,7 +205,7 @@ def train_climate_records(dataset, train_idx, val_idx, test_idx, epochs=1, batch
         val_batch, test_batch = (_upload(dataset.collate_val_host(ix, T_val, max_val_samples), dev)
                                  for ix in (val_idx, test_idx))
 
-    run = _Run(model_path, model_id, CLIMATE_METR_COLUMNS, log)
+    run = Run(model_path, model_id, CLIMATE_METR_COLUMNS, log, best_col=5, save_on_best=False)
     run.resume(model, optimizer, dev, resume_training, load_best)
 
     def plan_epoch(epoch):
@@ -298,7 +213,7 @@ def train_climate_records(dataset, train_idx, val_idx, test_idx, epochs=1, batch
         lists = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
         return lists, dataset.prepare_batches(lists, 'train') if device_collate else None
 
-    plan_ahead = plan_ahead and os.environ.get('NJODE_PLAN_AHEAD', '1') != '0'
+    plan_ahead = plan_ahead_on(plan_ahead)
     metrics, epoch_plan = [], {}
     while model.epoch <= epochs:
         t0 = time.time()

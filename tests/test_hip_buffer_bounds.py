@@ -130,11 +130,12 @@ class Row:
         m = self.m
         a = self.args(T)
         m._step_counter = STEP
-        dims, cb, cs, flags, keep, slot, sizes = m._make_call(
-            a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], kw['return_path'], kw['get_loss'], kw['until_T'],
-            self.M, save_bwd=kw.get('save_bwd', False), plan_only=True, rows_in_fwd=kw.get('rows_in_fwd', False))
-        return dict(dims=dims, cb=cb, cs=cs, flags=flags, keep=keep, slot=slot, sizes=sizes,
-                    get_loss=kw['get_loss'], n_rows=1 + sizes[3] + sizes[2])
+        c = m._describe_call(
+            a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], return_path=kw['return_path'],
+            get_loss=kw['get_loss'], until_T=kw['until_T'], M=self.M, save_bwd=kw.get('save_bwd', False),
+            rows_in_fwd=kw.get('rows_in_fwd', False))
+        return dict(dims=c.dims, cb=c.batch, cs=c.sched, flags=c.flags, keep=c.keep, slot=c.slot_i, sizes=c.sizes,
+                    get_loss=kw['get_loss'], n_rows=1 + c.sizes[3] + c.sizes[2])
 
     def release(self, S):
         torch.cuda.synchronize()
@@ -329,8 +330,9 @@ class Row:
         B, H = self.start_X.shape[0], m.hidden_size
         gh = RM.c_hT(B, H).cuda().contiguous()
         m._step_counter = STEP
-        call, sched, slot, _ = m._make_call(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], False, True, True,
-                                            self.M, save_bwd=True)
+        call = m._arm_call(m._describe_call(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], until_T=True,
+                                            M=self.M, save_bwd=True))
+        slot = call.slot_i
         try:
             ref_grad = m._grad_through_hT(call, gh).clone()
             ref = {'grad_params': ref_grad, 'hT': m._last_hT_replay.clone()}

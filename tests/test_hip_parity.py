@@ -341,9 +341,9 @@ def test_c_abi_error_codes():
     g = Golden('g1_bs_eval_B7')
     m = hip_model(g.cfg, g.state_dict()).eval()
     b = to_dev(g.batch())
-    call, sched, slot, B = m._make_call(b['times'], b['time_ptr'], b['X'], b['obs_idx'],
-                                        g.delta_t, g.T, b['start_X'], b['n_obs_ot'], False,
-                                        True, False, None, save_bwd=False)
+    call = m._arm_call(m._describe_call(b['times'], b['time_ptr'], b['X'], b['obs_idx'],
+                                        g.delta_t, g.T, b['start_X'], b['n_obs_ot']))
+    B = call.sizes[0]
     hT = torch.empty(B, 10, device='cuda')
     loss = torch.zeros(1, device='cuda')
     rc = L.njode_forward_f32(ctypes.byref(call.dims), m._flat.data_ptr(),
