@@ -44,7 +44,7 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_records_heldout', 'njode_records_val_bytes', 'njode_records_val_count',
            'njode_records_val_fill',
            # include/njode_selftest.h
-           'njode_selftest_dropout_words', 'njode_debug_plan_stamps')
+           'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
 SDE_MODELS = {'BlackScholes': 0, 'OrnsteinUhlenbeck': 1, 'Heston': 2}
 # (the fourth model is known to the staged entry points only: njode_generate_stage,
@@ -114,6 +114,33 @@ class NjodeRecordStore(C.Structure):
                 ('n_grid', C.c_int32), ('drop_unobserved', C.c_int32), ('reserved', C.c_int32),
                 ('row_ptr', C.c_void_p), ('row_g', C.c_void_p), ('vals', C.c_void_p),
                 ('mask', C.c_void_p), ('att_min', C.c_void_p), ('att_max', C.c_void_p)]
+
+
+class NjodePlanView(C.Structure):
+    """include/njode_selftest.h: byte offsets of a plan's arrays (-1: not part of this plan) and
+    which parts the call's plan defines."""
+    OFFSETS = ('sched', 't_of_row', 'first_row', 'last_row', 'item_prev', 'item_next', 'item_kbeg',
+               'item_len', 'order', 't_order', 'len_hist', 'base_s', 'base16_s', 'path_sorted',
+               'row_by_path', 'first_j', 'jlo', 'tile_base')
+    FLAGS = ('n_tiles', 'generic', 'seg', 'sort_linked', 'links_only', 'tails', 'one_launch',
+             'plan_first_stage', 'plan_blocks', 'cs_shift', 'cs_nwb', 'cs_large', 'scan_thread_per_key', 'lds_cnt',
+             'tail_radix', 'split_on')
+    _fields_ = ([('plan_bytes', C.c_int64)] + [(n, C.c_int64) for n in OFFSETS]
+                + [(n, C.c_int32) for n in FLAGS]
+                + [('split_ns', C.c_int32 * 2), ('split_nw', C.c_int32 * 2), ('split_r', C.c_float * 2)])
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n in ('plan_bytes',) + self.OFFSETS + self.FLAGS}
+        d.update(split_ns=list(self.split_ns), split_nw=list(self.split_nw), split_r=list(self.split_r))
+        return d
+
+
+def plan_view(dims, batch_size, n_obs, n_times, n_steps, call_flags):
+    """``njode_debug_plan_view`` as a dict."""
+    v = NjodePlanView()
+    check(lib().njode_debug_plan_view(C.byref(dims), batch_size, n_obs, n_times, n_steps, call_flags,
+                                      C.byref(v)))
+    return v.as_dict()
 
 
 class NjodeError(RuntimeError):
@@ -217,11 +244,13 @@ def lib():
                  'njode_records_heldout', 'njode_records_val_bytes', 'njode_records_val_count',
            'njode_records_val_fill',
            # include/njode_selftest.h
-           'njode_selftest_dropout_words', 'njode_debug_plan_stamps'):
+           'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view'):
         getattr(L, name).restype = C.c_int
     L.njode_selftest_dropout_words.argtypes = [u64, u64, C.c_uint32, C.c_uint32, i32, vp, vp]
     L.njode_selftest_dropout_words.restype = C.c_int
     L.njode_debug_plan_stamps.argtypes = [vp, C.c_int]
+    L.njode_debug_plan_view.argtypes = [C.POINTER(NjodeDims), i32, i32, i32, i32, i32,
+                                        C.POINTER(NjodePlanView)]
     _lib = L
     return L
 

@@ -343,6 +343,8 @@ int build_plan(const Layout& L, char* pw, const NjodeBatch* b, const NjodeSchedu
   int* bad = (int*)(pw + L.bad);
   HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
   if (nt > 0) HIP_TRY(hipMemsetAsync(dense, 0xFF, (size_t)nt * B * 4, st));
+  // (the plan's launches, all of them, as one entry of the profile)
+  ProfScope ps(L.seg ? "gen_plan.seg" : "gen_plan", st);
   if (n > 0) k_gen_rows<<<cdiv(n, 256), 256, 0, st>>>(time_ptr, nt, n, b->obs_idx, B, dense, bad);
   k_gen_jlo<<<cdiv(K + 2, 256), 256, 0, st>>>(k_jump, nt, K, (int*)(pw + L.jlo));
   if (L.seg) {
@@ -537,6 +539,33 @@ int gen_plan(const NjodeDims* dims, const NjodeBatch* b, const NjodeSchedule* s,
   const Layout L = make_layout(m, b->batch_size, b->n_obs, s->n_times, s->n_steps, call_flags);
   if (plan_bytes < L.plan_end) return fail(NJODE_E_WORKSPACE, "plan buffer too small: %zu < %zu", plan_bytes, L.plan_end);
   return build_plan(L, (char*)plan, b, s, st);
+}
+
+int gen_plan_view(const NjodeDims* dims, int B, int n_obs, int nt, int K, int call_flags, NjodePlanView* v) {
+  Model m;
+  const char* why;
+  if (!build_model(dims, m, &why)) return fail(NJODE_E_UNSUPPORTED, "generic kernels: %s", why);
+  const Layout L = make_layout(m, B, n_obs, nt, K, call_flags);
+  v->generic = 1;
+  v->plan_bytes = (int64_t)L.plan_end;
+  v->sched = (int64_t)L.sched;
+  v->jlo = (int64_t)L.jlo;
+  v->seg = L.seg ? 1 : 0;
+  if (!L.seg) return NJODE_OK;
+  v->t_of_row = (int64_t)L.t_of_row;
+  v->first_row = (int64_t)L.first_row;
+  v->last_row = (int64_t)L.last_row;
+  v->item_prev = (int64_t)L.item_prev;
+  v->item_next = (int64_t)L.item_next;
+  v->item_kbeg = (int64_t)L.item_kbeg;
+  v->item_len = (int64_t)L.item_len;
+  v->order = (int64_t)L.order;
+  v->t_order = (int64_t)L.tail_order;
+  v->tile_base = (int64_t)L.tile_base;
+  v->n_tiles = L.NT;
+  v->tails = 1;
+  v->tail_radix = 1;
+  return NJODE_OK;
 }
 
 int gen_forward(const NjodeDims* dims, const float* params, const NjodeBatch* b,

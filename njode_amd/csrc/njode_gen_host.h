@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/njode_hip.h"
+#include "../../include/njode_selftest.h"
 
 namespace njode {
 
@@ -17,6 +18,8 @@ int gen_workspace_bytes(const NjodeDims* dims, int B, int n_obs, int nt, int K, 
                         size_t* out, bool plan_only);
 int gen_plan(const NjodeDims* dims, const NjodeBatch* b, const NjodeSchedule* s, int call_flags,
              void* plan, size_t plan_bytes, hipStream_t st);
+// njode_debug_plan_view for this family: the offsets of the layout gen_plan builds into
+int gen_plan_view(const NjodeDims* dims, int B, int n_obs, int nt, int K, int call_flags, NjodePlanView* v);
 int gen_forward(const NjodeDims* dims, const float* params, const NjodeBatch* b,
                 const NjodeSchedule* s, int call_flags, float weight, float dropout_p,
                 uint64_t seed, float* hT, float* loss, float* path_h, float* path_y, void* ws,

@@ -17,7 +17,8 @@
 // on (first_stage = 2) behind k_row_time for large ones.
 //
 // Same arrays, bit for bit, as the multi-launch plan: the order is a stable counting sort whatever
-// the row-block size, the layout's sums are integers (tests/test_hip_switches.py).
+// the row-block size, the layout's sums are integers (tests/test_hip_switches.py through the output
+// bits; tests/test_hip_plan_arrays.py array by array against the host planner tests/plan_host.py).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include "../../include/njode_hip.h"
+#include "../../include/njode_selftest.h"
 #include "njode_plan.h"
 
 namespace njode {
@@ -41,5 +42,9 @@ bool pending_flush();
 // the call cannot host it.  pending_tails(hosted) goes behind that launch.
 void pending_host_or_flush(Call& c, hipStream_t st, PendingPlan& hosted);
 void pending_tails(const PendingPlan& p);
+
+// njode_debug_plan_view behind prepare(): which builder build_plan / plan_call would take for the
+// prepared call `c` in this process, and what that builder defines.  Launches nothing.
+void describe_plan(const Call& c, int call_flags, NjodePlanView* v);
 
 }  // namespace njode

@@ -294,6 +294,9 @@ __global__ void k_tail_keys(int B, const int* __restrict__ last_row,
 // returns hT.
 constexpr int TAIL_ORDER_MAX = 65536;
 constexpr int TAIL_BINS_MAX = 4096;
+// (asked by tail_order, plan_call and describe_plan alike) k_tail_order can sort these tails (else: the radix sort, and no deferred plan)
+bool tail_order_fits(int B, int K) { return B <= TAIL_ORDER_MAX && K <= TAIL_BINS_MAX; }
+bool tail_uses_radix(int B, int K) { return !tail_order_fits(B, K) || env().tail_sort_rocprim; }
 __global__ void __launch_bounds__(1024) k_tail_order(int B, int K, const int* __restrict__ last_row,
                                                      const int* __restrict__ t_of_row,
                                                      const int* __restrict__ k_jump,
@@ -435,10 +438,12 @@ hipError_t tail_order(Call& c, char* w, bool own_stream, hipStream_t st) {
     ts = c.side.st2;
     c.side.tails_sorted_on_st2 = 1;
   }
-  if (B <= TAIL_ORDER_MAX && K <= TAIL_BINS_MAX && !env().tail_sort_rocprim) {
+  if (!tail_uses_radix(B, K)) {
+    ProfScope ps("k_tail_order", ts);
     k_tail_order<<<1, 1024, 0, ts>>>(B, K, a.last_row, a.t_of_row, a.k_jump, (int*)a.t_order);
     return hipSuccess;
   }
+  ProfScope ps("k_tail_keys", ts);
   k_tail_keys<<<cdiv(B, 256), 256, 0, ts>>>(B, a.last_row, a.t_of_row, a.k_jump, tkey, tiota);
   size_t tmp = c.L.sort_tmp_bytes;
   return sort_pairs(w + c.L.sort_tmp, tmp, (const unsigned*)tkey, tkey_sorted, (const int*)tiota,
@@ -495,6 +500,17 @@ int cs_shift_for(int n, int K, int scan_chunks) {
 bool plan_is_dense(const Call& c) {
   return c.route.seg && c.route.size.dense_cells && !env().plan_sort && c.a.n_obs > 0;
 }
+// The questions build_plan, plan_call and describe_plan (njode_debug_plan_view) all ask, each stated once.
+// row-block shift of the multi-launch plan's counting sort; 0: rocPRIM's radix sort orders the rows
+int multi_launch_cs_shift(bool dense_plan, int n, int K) {
+  return (dense_plan && !env().sort_rocprim && n >= 16384 && K + 1 <= CS_KEYS) ? cs_shift_for(n, K, CS_SCAN_CHUNKS) : 0;
+}
+// an in-line plan of n rows is ONE whole launch (else: k_row_time, then the body from its third stage)
+bool inline_plan_whole(int n) { return n <= env().plan_inline_max; }
+int stage2_plan_blocks() { return std::min(std::max(env().plan_inline_blocks, 2), PLAN_BLOCKS_CAP); }
+// the one-launch plan's scan of the count table takes a thread per key (else a wave per key: njode_plan.h, stage 4)
+bool scan_thread_per_key(int cs_nwb) { return cs_nwb <= PLAN_SCAN_CHUNKS; }
+
 // The job of the call `c` whose plan prefix is at `w`; false: this plan is not one the single launch
 // builds (no dense matrix, a schedule that is too long for its LDS tables, NJODE_VALIDATE).
 // sched_src: device-visible pinned copy of the packed schedule, or null when it is already in place.
@@ -569,7 +585,9 @@ thread_local PendingPlan g_pending;
 namespace njode {
 
 void pending_tails(const PendingPlan& p) {
-  if (p.tails) k_tail_order<<<1, 1024, 0, p.st>>>(p.tB, p.tK, p.t_last_row, p.t_t_of_row, p.t_k_jump, p.t_order);
+  if (!p.tails) return;
+  ProfScope ps("k_tail_order", p.st);
+  k_tail_order<<<1, 1024, 0, p.st>>>(p.tB, p.tK, p.t_last_row, p.t_t_of_row, p.t_k_jump, p.t_order);
 }
 bool pending_flush() {
   if (!g_pending.on) return false;
@@ -609,7 +627,7 @@ int build_plan(Call& c, void* ws, hipStream_t st) {
   // (NJODE_PLAN_INLINE_MAX rows: 10 000 rows 58 us against ~70 us of launches; larger plans keep the
   // launches below, which fill the chip: 200 000 rows ~100 us against 137 us on 64 blocks)
   PlanJob job;
-  if (dense_plan && n <= env().plan_inline_max && fill_plan_job(c, w, nullptr, job)) {
+  if (dense_plan && inline_plan_whole(n) && fill_plan_job(c, w, nullptr, job)) {
     {
       ProfScope ps("k_plan_grid", st);
       arm_plan_job(job, st);
@@ -621,12 +639,14 @@ int build_plan(Call& c, void* ws, hipStream_t st) {
   }
   if (dense_plan) HIP_TRY(hipMemsetAsync(dense, 0xFF, (size_t)a.n_times * B * 4, st));
   // counting sort of the rows by length (kernels above): where its table fits
-  const int cs_shift = (dense_plan && !env().sort_rocprim && n >= 16384 && K + 1 <= CS_KEYS)
-                           ? cs_shift_for(n, K, CS_SCAN_CHUNKS) : 0;
+  const int cs_shift = multi_launch_cs_shift(dense_plan, n, K);
   const int cs_nwb = cs_shift ? cdiv(n, 1 << cs_shift) : 0;
   int* cs_tab = cs_shift ? (int*)(w + c.L.key_sorted) : nullptr;
-  k_row_time<<<cdiv(n, 256), 256, 0, st>>>(time_ptr, a.n_times, n, (int*)a.t_of_row, iota, K,
-                                           len_hist, a.obs_idx, B, dense);
+  {
+    ProfScope ps("k_row_time", st);
+    k_row_time<<<cdiv(n, 256), 256, 0, st>>>(time_ptr, a.n_times, n, (int*)a.t_of_row, iota, K,
+                                             len_hist, a.obs_idx, B, dense);
+  }
   if (validate) {
     k_validate_rows<<<cdiv(n, 256), 256, 0, st>>>(a.obs_idx, n, B, a.t_of_row, dense, a.n_obs_ot, vflag);
     int h = 0;
@@ -652,7 +672,7 @@ int build_plan(Call& c, void* ws, hipStream_t st) {
   // keeps the launches.
   if (dense_plan && env().plan_grid_tail && fill_plan_job(c, w, nullptr, job)) {
     job.first_stage = 2;
-    job.P = std::min(std::max(env().plan_inline_blocks, 2), PLAN_BLOCKS_CAP);
+    job.P = stage2_plan_blocks();
     arm_plan_job(job, st);
     {
       ProfScope ps("k_plan_grid", st);
@@ -667,11 +687,13 @@ int build_plan(Call& c, void* ws, hipStream_t st) {
   if (dense_plan) {
     // (the lockstep kernels need the path-major arrays of the sort below; the segment plan
     // only the links)
+    ProfScope ps("k_dense_link", st);
     k_dense_link<<<cdiv(B, 256), 256, 0, st>>>(B, a.n_times, K, dense, a.k_jump, (int*)a.first_row,
                                                (int*)a.last_row, (int*)a.item_prev,
                                                (int*)a.item_next, (int*)a.item_kbeg,
                                                (int*)a.item_len, sort_key, len_hist);
   } else {
+    ProfScope ps("k_link", st);
     HIP_TRY(sort_pairs(w + c.L.sort_tmp, tmp, (const unsigned*)a.obs_idx, (unsigned*)a.path_sorted,
                        (const int*)iota, (int*)a.row_by_path, n, bits_for((unsigned)(B - 1)), !env().sort_merge, st));
     k_link<<<cdiv(n, 256), 256, 0, st>>>(n, K, a.path_sorted, a.row_by_path, a.t_of_row, a.k_jump,
@@ -682,17 +704,22 @@ int build_plan(Call& c, void* ws, hipStream_t st) {
   if (c.route.seg) {
     unsigned* key_sorted = (unsigned*)(w + c.L.key_sorted);
     if (cs_tab) {
+      ProfScope ps("k_cs_scatter", st);
       k_cs_count<<<cdiv(cs_nwb, 4), 256, 0, st>>>(sort_key, n, K + 1, cs_nwb, cs_shift, cs_tab);
       k_cs_scan<<<K + 1, 64, 0, st>>>(cs_tab, len_hist, K, cs_nwb);
       k_cs_scatter<<<cdiv(cs_nwb, 4), 256, 0, st>>>(sort_key, n, K + 1, cs_nwb, cs_shift, cs_tab,
                                                    (int*)a.order);
     } else {
+      ProfScope ps("sort_rows_by_length", st);
       tmp = c.L.sort_tmp_bytes;
       HIP_TRY(sort_pairs(w + c.L.sort_tmp, tmp, (const unsigned*)sort_key, key_sorted,
                          (const int*)iota, (int*)a.order, n, bits_for((unsigned)K), !env().sort_merge, st));
     }
-    k_traj_layout<<<1, LAYOUT_THREADS, 0, st>>>(len_hist, n, K, (long long*)a.base_s,
-                                                (long long*)a.base16_s, split_cfg(a));
+    {
+      ProfScope ps("k_traj_layout", st);
+      k_traj_layout<<<1, LAYOUT_THREADS, 0, st>>>(len_hist, n, K, (long long*)a.base_s,
+                                                  (long long*)a.base16_s, split_cfg(a));
+    }
     if (c.route.tails) HIP_TRY(tail_order(c, w, cs_tab != nullptr, st));
   }
   HIP_TRY(hipGetLastError());
@@ -705,7 +732,7 @@ int plan_call(Call& c, const NjodeSchedule* sched, int call_flags, hipStream_t s
   if (call_flags & NJODE_C_PLAN_DEFER) {
     pending_flush();   // (an older job nobody hosted)
     PendingPlan& p = g_pending;
-    const bool tails_ok = !tails || (c.a.B <= TAIL_ORDER_MAX && c.a.K <= TAIL_BINS_MAX);
+    const bool tails_ok = !tails || tail_order_fits(c.a.B, c.a.K);
     if (tails_ok && fill_plan_job(c, c.pw, nullptr, p.job)) {
       // the schedule: read by the plan's first block from the caller's pinned copy when there is
       // one (no copy command on the queue), else copied now
@@ -732,6 +759,43 @@ int plan_call(Call& c, const NjodeSchedule* sched, int call_flags, hipStream_t s
   if ((rc = build_plan(c, c.pw, st))) return rc;
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
+}
+
+void describe_plan(const Call& c, int call_flags, NjodePlanView* v) {
+  const KArgs& a = c.a;
+  const int n = a.n_obs, B = a.B, K = a.K;
+  const bool dense = plan_is_dense(c);
+  v->seg = c.route.seg ? 1 : 0;
+  v->sort_linked = dense ? 0 : 1;
+  v->tails = c.route.tails ? 1 : 0;
+  PlanJob job;
+  const bool fits = n > 0 && fill_plan_job(c, c.pw, nullptr, job);
+  // (the same order of questions as plan_call and build_plan)
+  const bool tails_ok = !c.route.tails || tail_order_fits(B, K);
+  const bool deferred = (call_flags & NJODE_C_PLAN_DEFER) && tails_ok && fits;
+  const bool whole = deferred || (fits && inline_plan_whole(n));
+  const bool from2 = !whole && fits && env().plan_grid_tail;
+  v->one_launch = (whole || from2) ? 1 : 0;
+  v->plan_first_stage = from2 ? 2 : 0;
+  v->tail_radix = (c.route.tails && !deferred && tail_uses_radix(B, K)) ? 1 : 0;   // (a deferred plan's tails: k_tail_order)
+  if (v->one_launch) {
+    v->plan_blocks = from2 ? stage2_plan_blocks() : job.P;
+    v->links_only = job.last_stage <= 2 ? 1 : 0;
+    v->cs_shift = job.cs_shift;
+    v->cs_nwb = job.cs_nwb;
+    v->cs_large = job.cs_tab == (int*)(c.pw + c.L.key_sorted) ? 1 : 0;
+    v->scan_thread_per_key = scan_thread_per_key(job.cs_nwb) ? 1 : 0;
+    v->lds_cnt = 1;
+  } else if (c.route.seg && n > 0) {
+    const int sh = multi_launch_cs_shift(dense, n, K);
+    v->cs_shift = sh;
+    v->cs_nwb = sh ? cdiv(n, 1 << sh) : 0;
+    v->cs_large = sh ? 1 : 0;
+    v->lds_cnt = K <= SPLIT_KMAX ? 1 : 0;
+  }
+  const SplitCfg sc = split_cfg(a);
+  v->split_on = sc.on;
+  for (int i = 0; i < 2; ++i) { v->split_ns[i] = sc.ns[i]; v->split_nw[i] = sc.nw[i]; v->split_r[i] = sc.r[i]; }
 }
 
 void pending_host_or_flush(Call& c, hipStream_t st, PendingPlan& hosted) {
