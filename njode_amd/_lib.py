@@ -43,6 +43,9 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_records_bytes', 'njode_records_count', 'njode_records_fill',
            'njode_records_heldout', 'njode_records_val_bytes', 'njode_records_val_count',
            'njode_records_val_fill',
+           # include/njode_online.h
+           'njode_online_supported', 'njode_online_reset_f32', 'njode_online_advance_f32',
+           'njode_online_observe_f32', 'njode_online_predict_f32',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -114,6 +117,11 @@ class NjodeRecordStore(C.Structure):
                 ('n_grid', C.c_int32), ('drop_unobserved', C.c_int32), ('reserved', C.c_int32),
                 ('row_ptr', C.c_void_p), ('row_g', C.c_void_p), ('vals', C.c_void_p),
                 ('mask', C.c_void_p), ('att_min', C.c_void_p), ('att_max', C.c_void_p)]
+
+
+class NjodeOnlineState(C.Structure):
+    _fields_ = [('h', C.c_void_p), ('last_X', C.c_void_p), ('tau', C.c_void_p), ('now', C.c_void_p),
+                ('n_series', C.c_int32)]
 
 
 class NjodePlanView(C.Structure):
@@ -245,6 +253,15 @@ def lib():
            'njode_records_val_fill',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view'):
+        getattr(L, name).restype = C.c_int
+    dp, sp = C.POINTER(NjodeDims), C.POINTER(NjodeOnlineState)
+    L.njode_online_supported.argtypes = [dp]
+    L.njode_online_reset_f32.argtypes = [dp, vp, sp, vp, i32, vp, vp]
+    L.njode_online_advance_f32.argtypes = [dp, vp, sp, vp, i32, vp, f64, i32, vp, vp]
+    L.njode_online_observe_f32.argtypes = [dp, vp, sp, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp]
+    L.njode_online_predict_f32.argtypes = [dp, vp, sp, vp, i32, vp, i32, f64, i32, vp, vp, vp]
+    for name in ('njode_online_supported', 'njode_online_reset_f32', 'njode_online_advance_f32',
+                 'njode_online_observe_f32', 'njode_online_predict_f32'):
         getattr(L, name).restype = C.c_int
     L.njode_selftest_dropout_words.argtypes = [u64, u64, C.c_uint32, C.c_uint32, i32, vp, vp]
     L.njode_selftest_dropout_words.restype = C.c_int

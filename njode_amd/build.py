@@ -5,9 +5,9 @@ The kernels keep each lane's activations in registers, so every model *shape*
 is a separate template instantiation.  ``CONFIGS`` is the table of compiled
 shapes; ``NJODE_EXTRA_CONFIGS`` (env, ``;``-separated
 ``d,H,d_out,n_hidden,width,act,masked,current_t,residual,use_rnn``) appends to it.
-Each shape is compiled as six translation units (segment forward, segment
-backward, lockstep forward, lockstep backward, wave-per-path lockstep forward / sweep) so the
-build parallelises over the host cores.
+Each shape is compiled as seven translation units (segment forward, segment
+backward, lockstep forward, lockstep backward, wave-per-path lockstep forward / sweep, online
+filtering) so the build parallelises over the host cores.
 
 Usage:  python -m njode_amd.build [--force] [-j N]
 """
@@ -159,7 +159,7 @@ def build(force=False, jobs=None, verbose=True):
     common += os.environ.get('NJODE_EXTRA_FLAGS', '').split()   # kernel experiments
     tasks = []   # (object, command)
     for i, (d, h, do, nh, w, act, masked, curt, res, rnn) in enumerate(cfgs):
-        for part in range(6):
+        for part in range(7):
             obj = os.path.join(OBJ, 'cfg{}_{}.o'.format(i, part))
             defs = ['-DNJ_ID={}'.format(i), '-DNJ_PART={}'.format(part), '-DNJ_D={}'.format(d),
                     '-DNJ_H={}'.format(h), '-DNJ_DO={}'.format(do), '-DNJ_NH={}'.format(nh),
@@ -167,7 +167,7 @@ def build(force=False, jobs=None, verbose=True):
                     '-DNJ_MASKED={}'.format(masked), '-DNJ_CURT={}'.format(curt),
                     '-DNJ_RES={}'.format(res), '-DNJ_ACC_TANH={}'.format(masked), '-DNJ_RNN={}'.format(rnn)]
             tasks.append((obj, common + defs + [os.path.join(CSRC, 'njode_cfg.hip')]))
-    for unit in ('api', 'planner', 'prof', 'gen'):
+    for unit in ('api', 'planner', 'prof', 'gen', 'online'):
         tasks.append((os.path.join(OBJ, unit + '.o'), common + [os.path.join(CSRC, 'njode_{}.hip'.format(unit))]))
     # the batch producer spells out the reference's float64 expression trees: no contraction
     cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_producer.hip')]
@@ -206,7 +206,8 @@ def build(force=False, jobs=None, verbose=True):
     parts_only = os.environ.get('NJODE_PARTS_ONLY', '').strip()   # maintainer aid, e.g. "0": a change
     if parts_only:                                                 # that only touches those parts
         keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + (
-            'api.o', 'planner.o', 'prof.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o')
+            'api.o', 'planner.o', 'prof.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o',
+            'online.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
                 restamp(t)

@@ -1,7 +1,7 @@
 // njode_cfg.hip -- one model shape, compiled once per entry of the build table
 // (njode_amd/build.py) and per NJ_PART (0 segment forward + registration,
 // 1 segment backward, 2 lockstep forward, 3 lockstep backward, 4 / 5 the wave-per-path lockstep
-// forward / adjoint sweep of njode_chain.h) with
+// forward / adjoint sweep of njode_chain.h, 6 the online kernel of njode_online.h) with
 //   -DNJ_ID=.. -DNJ_D=.. -DNJ_H=.. -DNJ_DO=.. -DNJ_NH=.. -DNJ_W=.. -DNJ_ACT=..
 //   -DNJ_MASKED=.. -DNJ_CURT=.. -DNJ_RES=.. -DNJ_PART=..
 // Every launcher here takes the call's Route (njode_route.h) and switches on it: which kernel runs is
@@ -15,6 +15,9 @@
 #include "njode_chain.h"
 #include "njode_chain_seg.h"
 #include "njode_chain_dw.h"
+#endif
+#if NJ_PART == 6
+#include "njode_online.h"
 #endif
 
 #define NJ_CAT_(a, b) a##b
@@ -578,6 +581,33 @@ void NJ_CAT(njode_seg_chain_backward_, NJ_ID)(const KArgs& a, const Route& r, hi
 }
 void NJ_CAT(njode_chain_dw_, NJ_ID)(const KArgs& a, hipStream_t st) { chain_dw<C>(a, st); }
 void NJ_CAT(njode_chain_sweep_, NJ_ID)(const KArgs& a, const Route& r, hipStream_t st) { chain_sweep<C>(a, r, st); }
+#endif
+
+// Part 6, the online kernel (njode_online.hip finds the shape's entry by name: njode_online_ops_<id>)
+#if NJ_PART == 6
+template <class CC> static hipError_t online_launch(const OnlineArgs& a, int mode, hipStream_t st) {
+  if constexpr (OnlineOk<CC>::value) {
+    const dim3 grid(cdiv(a.n, a.spb)), block(64 * ONLINE_WAVES);
+    ProfScope ps("k_online", st);
+    if (mode == ONLINE_ADVANCE) k_online<CC, ONLINE_ADVANCE><<<grid, block, 0, st>>>(a);
+    else if (mode == ONLINE_OBSERVE) k_online<CC, ONLINE_OBSERVE><<<grid, block, 0, st>>>(a);
+    else if (mode == ONLINE_PREDICT) k_online<CC, ONLINE_PREDICT><<<grid, block, 0, st>>>(a);
+    else k_online<CC, ONLINE_RESET><<<grid, block, 0, st>>>(a);
+    return hipGetLastError();
+  } else {
+    return hipErrorNotSupported;
+  }
+}
+static hipError_t online_launch_c(const OnlineArgs& a, int mode, hipStream_t st) { return online_launch<C>(a, mode, st); }
+const OnlineOps* NJ_CAT(njode_online_ops_, NJ_ID)() {
+  static const OnlineOps ops = {
+      {NJ_D, NJ_H, NJ_DO, NJ_NH, (NJ_NH > 0 ? NJ_W : 0), NJ_ACT,
+       (NJ_MASKED ? NJODE_F_MASKED : 0) | (NJ_CURT ? NJODE_F_INPUT_CURRENT_T : 0) |
+           (NJ_RES ? NJODE_F_RESIDUAL : 0) | (NJ_RNN ? NJODE_F_USE_RNN : 0)},
+      OnlineOk<C>::value ? 1 : 0,
+      online_launch_c};
+  return &ops;
+}
 #endif
 
 }  // namespace njode

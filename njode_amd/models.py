@@ -549,3 +549,13 @@ class NJODE(FlatParams, CallLayer, torch.nn.Module):
             path_y = path_y.cpu()           # reference harness calls .numpy() on it
         return {'pred': path_y, 'pred_t': path_t}
 
+    # -- online filtering (not in the reference) ------------------------------------------
+    def online(self, n_series, delta_t):
+        """The resident state of ``n_series`` series (``njode_amd/online.py``: ``reset``,
+        ``observe``, ``advance``, ``predict``): each new measurement costs the Euler steps since the
+        last one instead of a ``get_pred`` over the whole history.  Eval mode; models with two
+        hidden layers per network and sizes up to 64, no GRU jump (``NotImplementedError``
+        otherwise)."""
+        from .online import OnlineState
+        return OnlineState(self, n_series, delta_t)
+

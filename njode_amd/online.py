@@ -1,0 +1,263 @@
+"""
+Online filtering with a trained NJ-ODE (C ABI: ``include/njode_online.h``).
+
+``NJODE.forward`` is the batch form: it starts at ``t = 0`` and needs the whole record.  An
+``OnlineState`` keeps ``(h, last_X, tau, now)`` of ``n_series`` series on the GPU; ``observe`` feeds
+the listed series their next measurement, ``predict`` reads forecasts from a copy of the state, and
+each call costs the Euler steps that are new.  The results of any sequence of calls on one series
+are those of the reference forward on the batch that consists of that series alone, with ``times``
+equal to the targets of the calls in order.
+
+``ids`` and times are host arrays (numpy or lists): they are checked here, on the host, and
+uploaded.  Values (``start_X``, ``X``, ``M``) are tensors or arrays; outputs are device tensors.
+Eval mode only, no loss, no gradients.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def default_max_steps(t, delta_t):
+    """``ceil(max(t) / delta_t) + 2``: since a clock is never negative, an upper bound of the Euler
+    steps the walk to any one of the targets ``t`` takes."""
+    t = np.asarray(t, dtype=np.float64)
+    top = float(t.max()) if t.size else 0.0
+    return max(int(math.ceil(top / float(delta_t))) + 2, 1)
+
+
+class OnlineState:
+    """The resident state of ``n_series`` series of ``model`` (``NJODE.online``)."""
+
+    def __init__(self, model, n_series, delta_t):
+        n_series, delta_t = int(n_series), float(delta_t)
+        if n_series <= 0:
+            raise ValueError('n_series must be positive, got {}'.format(n_series))
+        if not (delta_t > 0 and math.isfinite(delta_t)):
+            raise ValueError('delta_t must be positive and finite, got {!r}'.format(delta_t))
+        self.model, self.n_series, self.delta_t = model, n_series, delta_t
+        self.dims = model._get_dims()
+        L = _lib.lib()
+        if not L.njode_online_supported(ctypes.byref(self.dims)):
+            raise NotImplementedError('NJODE.online: ' + L.njode_last_error().decode('utf-8', 'replace'))
+        self.d, self.H, self.d_out = model.input_size, model.hidden_size, model.output_size
+        self.masked = bool(model.masked)
+        dev = next(model.parameters()).device
+        self.device = dev
+        self.h = torch.zeros(n_series, self.H, dtype=torch.float32, device=dev)
+        self.last_X = torch.zeros(n_series, self.d, dtype=torch.float32, device=dev)
+        self.tau = torch.zeros(n_series, dtype=torch.float32, device=dev)
+        self.now = torch.zeros(n_series, dtype=torch.float64, device=dev)
+        self.status = None      # the status tensor of the last advance / observe / predict call
+        self._pending = []      # (ids, status tensor) of the calls check() has not read yet
+
+    # -- host-side checks ---------------------------------------------------------------
+    def _eval_only(self):
+        if self.model.training:
+            raise ValueError('online filtering runs in eval mode only (no dropout): call model.eval()')
+
+    def _ids(self, ids, n=None):
+        """(host int32 ids or None, number of rows)."""
+        if ids is None:
+            if n is None or n > self.n_series:
+                raise ValueError('{} rows without ids, the state has {} series'.format(n, self.n_series))
+            return None, n
+        raw = np.asarray(ids)
+        if raw.ndim != 1 or (raw.size and not np.issubdtype(raw.dtype, np.integer)):
+            raise ValueError('ids must be a flat list of integers')
+        raw = raw.astype(np.int64)
+        if raw.size and (raw.min() < 0 or raw.max() >= self.n_series):
+            raise ValueError('ids out of range [0, {}): {}'.format(self.n_series, raw.tolist()))
+        if np.unique(raw).size != raw.size:
+            raise ValueError('duplicate ids in one call: {}'.format(raw.tolist()))
+        if n is not None and raw.size != n:
+            raise ValueError('{} ids for {} rows'.format(raw.size, n))
+        return raw.astype(np.int32), int(raw.size)
+
+    @staticmethod
+    def _times(t, shape):
+        t = np.asarray(t, dtype=np.float64)
+        if t.shape != shape:
+            raise ValueError('times of shape {}, expected {}'.format(t.shape, shape))
+        if not np.all(np.isfinite(t)) or np.any(t < 0):
+            raise ValueError('times must be finite and not negative')
+        return np.ascontiguousarray(t)
+
+    def _values(self, v, n, width, what):
+        v = torch.as_tensor(v)
+        if v.dim() != 2 or v.shape[0] != n or v.shape[1] != width:
+            raise ValueError('{} of shape {}, expected ({}, {})'.format(what, tuple(v.shape), n, width))
+        return v
+
+    def _rows(self, first, ids):
+        """Number of rows of a call: ``len(ids)``, else the leading size of its first array."""
+        if ids is not None:
+            return len(ids)
+        return int(np.shape(first)[0]) if np.ndim(first) else 1
+
+    # -- device side ----------------------------------------------------------------------
+    def _on_device(self):
+        if self.device.type != 'cuda':
+            raise RuntimeError('njode_amd online filtering runs on an MI355X only (the model is on {}); '
+                               'there is no CPU path.'.format(self.device))
+
+    def _up(self, a):
+        return None if a is None else torch.from_numpy(a).to(self.device)
+
+    def _f32(self, v):
+        return v.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _struct(self):
+        return _lib.NjodeOnlineState(self.h.data_ptr(), self.last_X.data_ptr(), self.tau.data_ptr(),
+                                     self.now.data_ptr(), self.n_series)
+
+    def _params(self):
+        m = self.model
+        m._ensure_flat(full=True)
+        if m._flat.device != self.device:
+            raise RuntimeError('model parameters moved to {}; the state is on {}'.format(m._flat.device, self.device))
+        return m._flat
+
+    def _status(self, ids, n):
+        st = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.status = st        # the last call's: one entry per row, 0 reached / 1 bound / 2 bad id
+        self._pending.append((np.arange(n) if ids is None else ids.copy(), st))
+        if len(self._pending) > 256:
+            self.check()
+        return st
+
+    # -- the calls --------------------------------------------------------------------------
+    def reset(self, start_X, ids=None):
+        """``h = encoder_map(start_X)`` (masked: mask 0), ``last_X = start_X``, ``tau = 0``, ``now = 0``."""
+        self._eval_only()
+        ids, n = self._ids(ids, None if ids is not None else self._rows(start_X, None))
+        x = self._values(start_X, n, self.d, 'start_X')
+        self._on_device()
+        P, x, ids_d = self._params(), self._f32(x), self._up(ids)
+        _lib.check(_lib.lib().njode_online_reset_f32(
+            ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
+            x.data_ptr(), _lib.stream_arg(self.device)))
+
+    def advance(self, t, ids=None, max_steps=None):
+        """An empty time slice at ``t`` (one time per listed series)."""
+        self._eval_only()
+        ids, n = self._ids(ids, None if ids is not None else self._rows(t, None))
+        t = self._times(t, (n,))
+        max_steps = default_max_steps(t, self.delta_t) if max_steps is None else int(max_steps)
+        self._on_device()
+        P, t_d, ids_d = self._params(), self._up(t), self._up(ids)
+        st = self._status(ids, n)
+        _lib.check(_lib.lib().njode_online_advance_f32(
+            ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
+            t_d.data_ptr(), self.delta_t, max_steps, st.data_ptr(), _lib.stream_arg(self.device)))
+
+    def observe(self, t, X, M=None, ids=None, max_steps=None, out=None):
+        """``advance(t)``, then the jump with observation ``X`` (masked models: and mask ``M``).
+        Returns ``(Y_before, Y)``, the readouts before and after the jump, ``[n, d_out]`` each
+        (``out``: a pair of device tensors to write them into)."""
+        self._eval_only()
+        ids, n = self._ids(ids, None if ids is not None else self._rows(X, None))
+        t = self._times(t, (n,))
+        x = self._values(X, n, self.d, 'X')
+        if self.masked and M is None:
+            raise ValueError('a masked model needs M')
+        if not self.masked and M is not None:
+            raise ValueError('M given to an unmasked model')
+        m = self._values(M, n, self.d, 'M') if self.masked else None
+        max_steps = default_max_steps(t, self.delta_t) if max_steps is None else int(max_steps)
+        self._on_device()
+        P, t_d, ids_d, x = self._params(), self._up(t), self._up(ids), self._f32(x)
+        m = self._f32(m) if m is not None else None
+        if out is None:
+            out = (torch.empty(n, self.d_out, dtype=torch.float32, device=self.device),
+                   torch.empty(n, self.d_out, dtype=torch.float32, device=self.device))
+        yb, y = out
+        st = self._status(ids, n)
+        _lib.check(_lib.lib().njode_online_observe_f32(
+            ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
+            t_d.data_ptr(), x.data_ptr(), _lib.ptr_arg(m), self.delta_t, max_steps, yb.data_ptr(),
+            y.data_ptr(), st.data_ptr(), _lib.stream_arg(self.device)))
+        return yb, y
+
+    def predict(self, t_query, ids=None, max_steps=None):
+        """Forecasts ``[n, Q, d_out]`` at the queries ``t_query [n, Q]`` (ascending per series) from a
+        copy of the state; the stored state is untouched.  A later query goes on from where the
+        earlier one stopped."""
+        self._eval_only()
+        ids, n = self._ids(ids, None if ids is not None else self._rows(t_query, None))
+        tq = np.asarray(t_query, dtype=np.float64)
+        if tq.ndim != 2 or tq.shape[0] != n or tq.shape[1] < 1:
+            raise ValueError('t_query of shape {}, expected ({}, Q >= 1)'.format(tq.shape, n))
+        tq = self._times(tq, tq.shape)
+        if np.any(np.diff(tq, axis=1) < 0):
+            raise ValueError('the queries of a series must ascend')
+        Q = tq.shape[1]
+        max_steps = default_max_steps(tq, self.delta_t) if max_steps is None else int(max_steps)
+        self._on_device()
+        P, t_d, ids_d = self._params(), self._up(tq), self._up(ids)
+        y = torch.empty(n, Q, self.d_out, dtype=torch.float32, device=self.device)
+        st = self._status(ids, n)
+        _lib.check(_lib.lib().njode_online_predict_f32(
+            ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
+            t_d.data_ptr(), Q, self.delta_t, max_steps, y.data_ptr(), st.data_ptr(),
+            _lib.stream_arg(self.device)))
+        return y
+
+    def replay(self, times, time_ptr, X, obs_idx, M=None):
+        """Feed a collated batch slice by slice (``obs_idx``: the series of each row): a warm start
+        from history.  A slice without rows moves nobody.  Returns ``(Y_before, Y)``, one row per
+        row of ``X``."""
+        self._eval_only()
+        times = np.asarray(times, dtype=np.float64)
+        ptr = np.asarray(time_ptr, dtype=np.int64)
+        idx = np.asarray(obs_idx.cpu() if torch.is_tensor(obs_idx) else obs_idx).astype(np.int64)
+        if ptr.shape != (times.size + 1,) or ptr[0] != 0 or ptr[-1] != idx.size or np.any(np.diff(ptr) < 0):
+            raise ValueError('time_ptr does not describe {} slices of {} rows'.format(times.size, idx.size))
+        x = self._values(X, idx.size, self.d, 'X')
+        if self.masked and M is None:
+            raise ValueError('a masked model needs M')
+        if not self.masked and M is not None:
+            raise ValueError('M given to an unmasked model')
+        m = self._values(M, idx.size, self.d, 'M') if self.masked else None
+        self._on_device()
+        x = self._f32(x)
+        m = self._f32(m) if m is not None else None
+        yb = torch.empty(idx.size, self.d_out, dtype=torch.float32, device=self.device)
+        y = torch.empty_like(yb)
+        for i, t in enumerate(times):
+            lo, hi = int(ptr[i]), int(ptr[i + 1])
+            if hi > lo:
+                self.observe(np.full(hi - lo, t), x[lo:hi], None if m is None else m[lo:hi], ids=idx[lo:hi],
+                             out=(yb[lo:hi], y[lo:hi]))
+        return yb, y
+
+    # -- bookkeeping ------------------------------------------------------------------------
+    def check(self):
+        """Read the status of every call since the last check (synchronises); ``RuntimeError`` naming
+        the series that the step bound stopped."""
+        pending, self._pending = self._pending, []
+        stopped, bad = set(), set()
+        for ids, st in pending:
+            s = st.cpu().numpy()
+            stopped.update(int(i) for i in ids[s == 1])
+            bad.update(int(i) for i in ids[s == 2])
+        if bad:
+            raise RuntimeError('online: ids outside the state: {}'.format(sorted(bad)))
+        if stopped:
+            raise RuntimeError('online: series {} hit max_steps before their target; their state is where '
+                               'the bound stopped them'.format(sorted(stopped)))
+
+    def state_dict(self):
+        return {'h': self.h.clone(), 'last_X': self.last_X.clone(), 'tau': self.tau.clone(),
+                'now': self.now.clone(), 'delta_t': self.delta_t}
+
+    def load_state_dict(self, sd):
+        for k, t in (('h', self.h), ('last_X', self.last_X), ('tau', self.tau), ('now', self.now)):
+            src = torch.as_tensor(sd[k])
+            if src.shape != t.shape:
+                raise ValueError('{} of shape {}, expected {}'.format(k, tuple(src.shape), tuple(t.shape)))
+            t.copy_(src.to(device=t.device, dtype=t.dtype))
+        self.delta_t = float(sd.get('delta_t', self.delta_t))

@@ -1,0 +1,140 @@
+"""Online filtering against what the same answer costs on the batch route.
+
+    python tools/ubench/online_bench.py [--out profiles/online_bench.jsonl]
+
+Per shape (demo: d = 1, H = 10, delta_t = 0.01; PhysioNet: d = H = 41, delta_t = 0.016 / 48) and
+per number of resident series N = 1, 50, 1 000, one line with
+
+* ``observe`` when the target is 1 Euler step ahead and when it is 30 steps ahead, every series of
+  the state in one call, and ``predict`` with Q = 8 queries 4 steps apart: GPU time between HIP
+  events on the current stream (the kernel and the upload of ids and times in front of it), and
+  the wall clock around a device synchronise (what a caller waits for: host checks included);
+  ``step_us`` = (observe 30 - observe 1) / 29 of the GPU medians -- a lone wave is latency-bound,
+  so read it against the 0.27 / 0.63 us per Euler step of the wave-per-path kernels;
+* the yardstick, code this feature does not touch: ``NJODE.get_pred`` over the series' full
+  history on [0, 1] (100 Euler steps for the demo shape, 3 000 for PhysioNet), which is what an
+  answer to "what do you predict now?" costs without a resident state.
+
+One process, warm-up calls first, medians (and the fastest call) after them.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from njode_amd import data_utils, models, synthetic_physionet  # noqa: E402
+
+NN = ((50, 'tanh'), (50, 'tanh'))
+
+
+def med_min(ms):
+    return [float(np.median(ms)), float(np.min(ms))]
+
+
+def timed(fn, warmup, reps):
+    """(GPU ms between events, wall ms around a synchronise), median and minimum of each."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    gpu, wall = [], []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        gpu.append(a.elapsed_time(b))
+    return med_min(gpu), med_min(wall)
+
+
+def history(shape, N):
+    """(model, batch, delta_t, T) of ``N`` series observed on [0, 1]."""
+    torch.manual_seed(0)
+    if shape == 'demo':
+        import copy
+        hp = copy.deepcopy(data_utils.hyperparam_default)
+        hp.update(nb_paths=N, nb_steps=100, obs_perc=0.1)
+        paths, obs, nb_obs, meta = data_utils.create_dataset('BlackScholes', hp, seed=0)
+        b = data_utils.collate_arrays(paths, obs, nb_obs, meta['dt'])
+        m = models.NJODE(1, 10, 1, NN, NN, NN, False, options={'device_outputs': True})
+        return m.to('cuda').eval(), b, meta['dt'], meta['maturity']
+    b = synthetic_physionet.make_batch(batch_size=N, n_grid=3000, seed=0)
+    m = models.NJODE(41, 41, 41, NN, NN, NN, False, options={'device_outputs': True, 'masked': True})
+    return m.to('cuda').eval(), b, b['delta_t'], b['T']
+
+
+def case(shape, N, reps):
+    m, b, delta_t, T = history(shape, N)
+    d = b['start_X'].shape[1]
+    dev = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
+    M = dev.get('M')
+
+    def get_pred():
+        return m.get_pred(dev['times'], dev['time_ptr'], dev['X'], dev['obs_idx'], delta_t, T, dev['start_X'], M=M)
+
+    st = m.online(N, delta_t)
+    st.reset(dev['start_X'])
+    st.replay(b['times'], b['time_ptr'], dev['X'], b['obs_idx'], M)      # a warm start from the history
+    st.check()
+    X = torch.rand(N, d, device='cuda')
+    Mo = (torch.rand(N, d, device='cuda') < 0.15).float() if M is not None else None
+    clock = {'t': float(T)}
+
+    def observe(k):
+        def fn():
+            clock['t'] += k * delta_t
+            st.observe(np.full(N, clock['t']), X, Mo)
+        return fn
+
+    def predict():
+        q = clock['t'] + 4 * delta_t * np.arange(1, 9)
+        st.predict(np.broadcast_to(q, (N, 8)))
+
+    # the routes alternate so that none owns a quieter stretch of the machine
+    res = {'obs1': [], 'obs30': [], 'pred8': [], 'get_pred': []}
+    for rnd in range(2):
+        w = 3 if rnd == 0 else 0
+        res['obs1'].append(timed(observe(1), w, reps))
+        res['obs30'].append(timed(observe(30), w, reps))
+        res['pred8'].append(timed(predict, w, reps))
+        res['get_pred'].append(timed(get_pred, 2 if rnd == 0 else 0, max(reps // 8, 3)))
+    st.check()
+    best = {k: min(v, key=lambda r: r[0][0]) for k, v in res.items()}      # the quieter round
+    g1, g30 = best['obs1'][0][0], best['obs30'][0][0]
+    return {
+        'case': 'online {} N={}'.format(shape, N), 'shape': shape, 'N': N, 'delta_t': delta_t,
+        'history_euler_steps': int(round(T / delta_t)), 'history_rows': int(b['time_ptr'][-1]),
+        'observe_1_step_gpu_ms_median_min': best['obs1'][0], 'observe_1_step_wall_ms_median_min': best['obs1'][1],
+        'observe_30_steps_gpu_ms_median_min': best['obs30'][0],
+        'observe_30_steps_wall_ms_median_min': best['obs30'][1],
+        'predict_q8_32_steps_gpu_ms_median_min': best['pred8'][0],
+        'predict_q8_32_steps_wall_ms_median_min': best['pred8'][1],
+        'step_us': (g30 - g1) / 29.0 * 1e3,
+        'get_pred_full_history_gpu_ms_median_min': best['get_pred'][0],
+        'get_pred_full_history_wall_ms_median_min': best['get_pred'][1],
+        'get_pred_over_observe_1_step_wall': best['get_pred'][1][0] / best['obs1'][1][0],
+        'both_rounds_gpu_ms_median': {k: [r[0][0] for r in v] for k, v in res.items()},
+    }
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--reps', type=int, default=40)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs a GPU: there is nothing to measure without one'
+    for shape in ('demo', 'physionet'):
+        for N in (1, 50, 1000):
+            line = json.dumps(case(shape, N, a.reps))
+            print(line, flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, 'a') as f:
+                    f.write(line + '\n')
