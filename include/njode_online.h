@@ -98,6 +98,59 @@ int njode_online_predict_f32(const NjodeDims* dims, const float* params, const N
                              double delta_t, int32_t max_steps, float* Y, int32_t* status,
                              njodeStream_t stream);
 
+/* ---- The same calls on the shape-generic matrix-core kernels --------------------------------------
+ * For the models njode_online_supported refuses: any sizes within the envelope of njode_supported's
+ * generic family, 0 .. NJODE_MAX_HIDDEN hidden layers, per-network descriptions (per_net = 1), tanh /
+ * relu, every residual case, input_current_t, masked (input_size == output_size), unmasked with
+ * output_size != input_size, and the GRU jump (use_rnn, 4 hidden_size <= 1024, masked or not; the
+ * cell sees X as given).  The state is the same NjodeOnlineState: on a shape both families accept
+ * it moves freely between them.  Semantics, status values, the clock and the bound are those
+ * above, word for word; the results for a series are the bits njode_forward_f32 gives on the batch
+ * of that series alone where that call runs the generic family.
+ *
+ * One workgroup per tile of `series_per_tile` listed series (0: the smallest power of two <= 16
+ * with at most 256 tiles; else 1, 2, 4, 8 or 16).  A series' results do not depend on the tile
+ * size, on its place in the tile or on the other series of the call.  No atomics.
+ *
+ * `tables`: device buffer of njode_online_tables_bytes() bytes, owned by the caller, filled by
+ * njode_online_tables_f32 from `params` on the caller's stream and read by the four calls.  It
+ * must be filled again whenever the parameters change.
+ *
+ * NJODE_E_BADARG -- before anything is launched -- for everything the entry points above refuse,
+ * a null `tables`, tables_bytes below njode_online_tables_bytes() and a series_per_tile outside
+ * {0, 1, 2, 4, 8, 16}; NJODE_E_UNSUPPORTED for a model njode_online_gen_supported refuses. */
+
+/* 1 if the njode_online_gen_* entry points run this model, else 0; the reason, "online: ...", is
+ * left in njode_last_error().  A pure host function. */
+int njode_online_gen_supported(const NjodeDims* dims);
+
+int njode_online_tables_bytes(const NjodeDims* dims, size_t* out);
+
+int njode_online_tables_f32(const NjodeDims* dims, const float* params, void* tables, size_t tables_bytes,
+                            njodeStream_t stream);
+
+int njode_online_gen_reset_f32(const NjodeDims* dims, const float* params, const void* tables,
+                               size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                               int32_t n, const float* start_X, int32_t series_per_tile,
+                               njodeStream_t stream);
+
+int njode_online_gen_advance_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                 size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                 int32_t n, const double* t, double delta_t, int32_t max_steps,
+                                 int32_t series_per_tile, int32_t* status, njodeStream_t stream);
+
+int njode_online_gen_observe_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                 size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                 int32_t n, const double* t, const float* X, const float* M,
+                                 double delta_t, int32_t max_steps, int32_t series_per_tile,
+                                 float* Y_before, float* Y, int32_t* status, njodeStream_t stream);
+
+int njode_online_gen_predict_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                 size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                 int32_t n, const double* t_query, int32_t Q, double delta_t,
+                                 int32_t max_steps, int32_t series_per_tile, float* Y, int32_t* status,
+                                 njodeStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

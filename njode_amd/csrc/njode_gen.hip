@@ -1,7 +1,8 @@
 // njode_gen.hip -- host side of the shape-generic kernel family (njode_gen.h): model
 // description -> layer tables, workspace layout, plan (dense [time][path] -> row matrix, first
 // jump of every Euler step), launches.  Entry points are the gen_* functions below; the C ABI
-// (njode_api.hip) routes to them every model shape the build table has no specialisation for.
+// (njode_api.hip) routes to them every model shape the build table has no specialisation for.  The
+// njode_online_gen_* entry points (include/njode_online.h) are at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -11,7 +12,9 @@
 #include "njode_env.h"
 #include "njode_gen.h"
 #include "njode_gen_seg.h"
+#include "njode_gen_online.h"
 #include "njode_gen_host.h"
+#include "njode_online_check.h"
 
 using namespace njode;
 using namespace njode::gen;
@@ -377,6 +380,18 @@ int build_plan(const Layout& L, char* pw, const NjodeBatch* b, const NjodeSchedu
   return NJODE_OK;
 }
 
+// output tiles per wave of every layer, forward and transposed product, at nw waves per workgroup
+void tiles_per_wave(GArgs& a, int nw) {
+  GNet* nets[3] = {&a.ode, &a.enc, &a.dec};
+  for (GNet* N : nets)
+    for (int l = 0; l < N->nl; ++l) {
+      N->l[l].per = cdiv(N->l[l].MT, nw);
+      N->l[l].pert = cdiv(N->l[l].MTT, nw);
+    }
+  a.gru.l[0].per = cdiv(a.gru.l[0].MT, nw);
+  a.gru.l[0].pert = cdiv(a.gru.l[0].MTT, nw);
+}
+
 struct Call {
   Model m;
   Layout L;
@@ -451,17 +466,7 @@ int prepare(Call& c, const NjodeDims* dims, const float* params, const NjodeBatc
     const int n_cu = device_cu_count();
     if (env().gen_nw == -1 && c.m.nw > 4 && (long long)c.L.NT >= 16LL * n_cu) c.m.nw = 4;
   }
-  {
-    // output tiles per wave, now that the waves per workgroup are known
-    GNet* nets[3] = {&a.ode, &a.enc, &a.dec};
-    for (GNet* N : nets)
-      for (int l = 0; l < N->nl; ++l) {
-        N->l[l].per = cdiv(N->l[l].MT, c.m.nw);
-        N->l[l].pert = cdiv(N->l[l].MTT, c.m.nw);
-      }
-    a.gru.l[0].per = cdiv(a.gru.l[0].MT, c.m.nw);
-    a.gru.l[0].pert = cdiv(a.gru.l[0].MTT, c.m.nw);
-  }
+  tiles_per_wave(a, c.m.nw);   // (now that the waves per workgroup are known)
   if (c.L.seg) {
     GSeg& g = c.g;
     g.order = (const int*)(pw + c.L.order);
@@ -710,6 +715,164 @@ int gen_backward(const NjodeDims* dims, const float* params, const NjodeBatch* b
 
 }  // namespace gen
 }  // namespace njode
+
+// =============================================================================================
+// online filtering on this family (njode_gen_online.h): the njode_online_gen_* entry points of
+// include/njode_online.h.  One build_model per call; the argument checks shared with the wave
+// family are njode_online_check.h's.
+// =============================================================================================
+namespace {
+
+// The verdict is build_model's, plus the per-chain clock arrays behind the LDS carve-up.  The
+// reason, either way, is left in njode_last_error().
+bool online_model(const NjodeDims* dims, Model& m) {
+  const char* why;
+  if (!build_model(dims, m, &why)) {
+    fail(NJODE_E_UNSUPPORTED, "online: %s", why);
+    return false;
+  }
+  m.lds_bytes += GON_CLOCK_FLOATS * 4;
+  if (m.lds_bytes > LDS_LIMIT) {
+    fail(NJODE_E_UNSUPPORTED, "online: the LDS images and the per-chain clocks exceed the 160 KB LDS of a workgroup");
+    return false;
+  }
+  fail(NJODE_OK, "online: a tile of up to 16 series per workgroup of %d waves on the matrix cores (d = %d, H = %d, d_out = %d)",
+       m.nw, m.a.D, m.a.H, m.a.DO);
+  return true;
+}
+size_t online_tables_bytes(const Model& m) { return (size_t)m.frag_floats * 4; }
+
+// the verdict, then the checks of the tables every entry point shares
+int online_tables(const NjodeDims* dims, const void* tables, size_t tables_bytes, Model& m) {
+  if (!dims) return fail(NJODE_E_BADARG, "online: null dims");
+  if (!online_model(dims, m)) return NJODE_E_UNSUPPORTED;   // (the reason is in place)
+  if (!tables) return fail(NJODE_E_BADARG, "online: null tables");
+  if (tables_bytes < online_tables_bytes(m))
+    return fail(NJODE_E_BADARG, "online: tables_bytes = %zu < %zu", tables_bytes, online_tables_bytes(m));
+  return NJODE_OK;
+}
+int online_common(const NjodeDims* dims, const float* params, const void* tables, size_t tables_bytes,
+                  const NjodeOnlineState* s, const int32_t* ids, int32_t n, int32_t series_per_tile, Model& m,
+                  OnlineArgs* o) {
+  if (int rc = online_tables(dims, tables, tables_bytes, m)) return rc;
+  if (int rc = online_state(params, s, ids, n, o)) return rc;
+  const int p = series_per_tile;
+  if (p != 0 && p != 1 && p != 2 && p != 4 && p != 8 && p != 16)
+    return fail(NJODE_E_BADARG, "online: series_per_tile = %d (0, 1, 2, 4, 8 or 16)", p);
+  return NJODE_OK;
+}
+int online_launch(const Model& m, const void* tables, const OnlineArgs& o, int mode, int series_per_tile,
+                  njodeStream_t stream) {
+  if (o.n == 0) return NJODE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  GArgs a = m.a;
+  a.P = o.P;
+  a.frag = (const float*)tables;
+  tiles_per_wave(a, m.nw);
+  // series per tile: the smallest power of two <= 16 with at most 256 tiles (gen_paths_per_tile
+  // without its record term), unless the caller fixes it
+  int PT = series_per_tile ? series_per_tile : 1;
+  while (!series_per_tile && PT < 16 && cdiv(o.n, PT) > 256) PT *= 2;
+  if (int rc = set_lds((const void*)k_gen_online, m.lds_bytes)) return rc;
+  {
+    ProfScope ps("k_gen_online", st);
+    k_gen_online<<<cdiv(o.n, PT), m.nw * 64, m.lds_bytes, st>>>(a, o, PT, mode);
+  }
+  HIP_TRY(hipGetLastError());
+  return NJODE_OK;
+}
+
+}  // namespace
+
+extern "C" int njode_online_gen_supported(const NjodeDims* dims) {
+  Model m;
+  if (!dims) {
+    fail(NJODE_E_BADARG, "online: null dims");
+    return 0;
+  }
+  return online_model(dims, m) ? 1 : 0;
+}
+
+extern "C" int njode_online_tables_bytes(const NjodeDims* dims, size_t* out) {
+  Model m;
+  if (!dims || !out) return fail(NJODE_E_BADARG, "online: null dims or out");
+  if (!online_model(dims, m)) return NJODE_E_UNSUPPORTED;
+  *out = online_tables_bytes(m);
+  return NJODE_OK;
+}
+
+extern "C" int njode_online_tables_f32(const NjodeDims* dims, const float* params, void* tables, size_t tables_bytes,
+                                       njodeStream_t stream) {
+  Model m;
+  if (int rc = online_tables(dims, tables, tables_bytes, m)) return rc;
+  if (!params) return fail(NJODE_E_BADARG, "online: null params");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("k_gen_pack", st);
+  k_gen_pack<<<cdiv(m.pack.total, 256), 256, 0, st>>>(params, (float*)tables, m.pack);
+  HIP_TRY(hipGetLastError());
+  return NJODE_OK;
+}
+
+extern "C" int njode_online_gen_reset_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                          size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                          int32_t n, const float* start_X, int32_t series_per_tile,
+                                          njodeStream_t stream) {
+  Model m;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, tables, tables_bytes, state, ids, n, series_per_tile, m, &a)) return rc;
+  if (!start_X) return fail(NJODE_E_BADARG, "online: null start_X");
+  a.X = start_X;
+  return online_launch(m, tables, a, ONLINE_RESET, series_per_tile, stream);
+}
+
+extern "C" int njode_online_gen_advance_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                            size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                            int32_t n, const double* t, double delta_t, int32_t max_steps,
+                                            int32_t series_per_tile, int32_t* status, njodeStream_t stream) {
+  Model m;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, tables, tables_bytes, state, ids, n, series_per_tile, m, &a)) return rc;
+  if (int rc = online_clock(delta_t, max_steps, t, status, &a)) return rc;
+  a.status = status;
+  return online_launch(m, tables, a, ONLINE_ADVANCE, series_per_tile, stream);
+}
+
+extern "C" int njode_online_gen_observe_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                            size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                            int32_t n, const double* t, const float* X, const float* M,
+                                            double delta_t, int32_t max_steps, int32_t series_per_tile,
+                                            float* Y_before, float* Y, int32_t* status, njodeStream_t stream) {
+  Model m;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, tables, tables_bytes, state, ids, n, series_per_tile, m, &a)) return rc;
+  if (int rc = online_clock(delta_t, max_steps, t, status, &a)) return rc;
+  if (!X) return fail(NJODE_E_BADARG, "online: null X");
+  if (m.a.masked && !M) return fail(NJODE_E_BADARG, "online: a masked model needs M");
+  if (!m.a.masked && M) return fail(NJODE_E_BADARG, "online: M given to an unmasked model");
+  a.X = X;
+  a.M = M;
+  a.Y_before = Y_before;
+  a.Y = Y;
+  a.status = status;
+  return online_launch(m, tables, a, ONLINE_OBSERVE, series_per_tile, stream);
+}
+
+extern "C" int njode_online_gen_predict_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                            size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                            int32_t n, const double* t_query, int32_t Q, double delta_t,
+                                            int32_t max_steps, int32_t series_per_tile, float* Y, int32_t* status,
+                                            njodeStream_t stream) {
+  Model m;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, tables, tables_bytes, state, ids, n, series_per_tile, m, &a)) return rc;
+  if (int rc = online_clock(delta_t, max_steps, t_query, status, &a)) return rc;
+  if (Q <= 0) return fail(NJODE_E_BADARG, "online: Q = %d", Q);
+  if (!Y) return fail(NJODE_E_BADARG, "online: null Y");
+  a.Q = Q;
+  a.Y = Y;
+  a.status = status;
+  return online_launch(m, tables, a, ONLINE_PREDICT, series_per_tile, stream);
+}
 
 #ifdef NJ_GEN_STAMPS
 // diagnostic build only: read and clear the phase stamps of njode_gen.h

@@ -1,13 +1,14 @@
 // njode_online.hip -- the online entry points of libnjode_hip.so (include/njode_online.h): argument
 // checks, the verdict on a shape, and the launch of the shape's kernel (njode_cfg.hip, part 6:
-// njode_online.h).  Host code only; nothing is kept between calls.
+// njode_online.h).  The njode_online_gen_* functions live in njode_gen.hip, beside build_model; both
+// share the checks of njode_online_check.h.  Host code only; nothing is kept between calls.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/njode_online.h"
 #include "njode_hostlib.h"
-#include "njode_online_args.h"
+#include "njode_online_check.h"
 
 using namespace njode;
 
@@ -83,38 +84,7 @@ int online_common(const NjodeDims* dims, const float* params, const NjodeOnlineS
   if (!dims) return fail(NJODE_E_BADARG, "online: null dims");
   *ops = online_find(dims);
   if (!*ops) return NJODE_E_UNSUPPORTED;   // (the reason is in place)
-  if (!params) return fail(NJODE_E_BADARG, "online: null params");
-  if (!s || !s->h || !s->last_X || !s->tau || !s->now) return fail(NJODE_E_BADARG, "online: null state or state array");
-  if (s->n_series <= 0) return fail(NJODE_E_BADARG, "online: n_series = %d", s->n_series);
-  if (n < 0) return fail(NJODE_E_BADARG, "online: n = %d", n);
-  if (!ids && n > s->n_series) return fail(NJODE_E_BADARG, "online: n = %d rows without ids, n_series = %d", n, s->n_series);
-  *a = OnlineArgs{};
-  a->P = params;
-  a->h = s->h;
-  a->last_X = s->last_X;
-  a->tau = s->tau;
-  a->now = s->now;
-  a->n_series = s->n_series;
-  a->ids = ids;
-  a->n = n;
-  a->Q = 1;
-  a->max_steps = 1;
-  // as few series per block as still give every block a CU of its own: a lone wave is
-  // latency-bound, and the block's other waves only help to fill the tables
-  a->spb = 1;
-  while (a->spb < ONLINE_WAVES && cdiv(n, a->spb) > 256) a->spb *= 2;
-  return NJODE_OK;
-}
-int online_clock(double delta_t, int32_t max_steps, const double* t, const int32_t* status, OnlineArgs* a) {
-  if (!(delta_t > 0.0) || !std::isfinite(delta_t))
-    return fail(NJODE_E_BADARG, "online: delta_t = %g must be positive and finite", delta_t);
-  if (max_steps <= 0) return fail(NJODE_E_BADARG, "online: max_steps = %d", max_steps);
-  if (!t || !status) return fail(NJODE_E_BADARG, "online: null t or status");
-  a->t = t;
-  a->delta_t = delta_t;
-  a->eps_dt = 1e-10 * delta_t;
-  a->max_steps = max_steps;
-  return NJODE_OK;
+  return online_state(params, s, ids, n, a);
 }
 int online_run(const OnlineOps* ops, const OnlineArgs& a, int mode, njodeStream_t stream) {
   if (a.n == 0) return NJODE_OK;

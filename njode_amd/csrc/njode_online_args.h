@@ -1,5 +1,6 @@
 // njode_online_args.h -- what the online entry points (njode_online.hip) hand to the per-shape
-// kernel unit (njode_cfg.hip, part 6: njode_online.h).  Plain data, host and device.
+// kernel unit (njode_cfg.hip, part 6: njode_online.h), and those of njode_gen.hip to k_gen_online
+// (njode_gen_online.h; it ignores spb).  Plain data, host and device.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -550,12 +550,14 @@ class NJODE(FlatParams, CallLayer, torch.nn.Module):
         return {'pred': path_y, 'pred_t': path_t}
 
     # -- online filtering (not in the reference) ------------------------------------------
-    def online(self, n_series, delta_t):
+    def online(self, n_series, delta_t, kernels='wave'):
         """The resident state of ``n_series`` series (``njode_amd/online.py``: ``reset``,
         ``observe``, ``advance``, ``predict``): each new measurement costs the Euler steps since the
-        last one instead of a ``get_pred`` over the whole history.  Eval mode; models with two
-        hidden layers per network and sizes up to 64, no GRU jump (``NotImplementedError``
-        otherwise)."""
+        last one instead of a ``get_pred`` over the whole history.  Eval mode.  ``kernels='wave'``
+        (the default): models with two hidden layers per network and sizes up to 64, no GRU jump
+        (``NotImplementedError`` otherwise); ``kernels='generic'``: every model the shape-generic
+        kernels run -- wider and deeper networks, ``nn_desc = None``, ``use_rnn``; ``'auto'``: the
+        first where it applies, else the second."""
         from .online import OnlineState
-        return OnlineState(self, n_series, delta_t)
+        return OnlineState(self, n_series, delta_t, kernels=kernels)
 

@@ -4,7 +4,12 @@ Online filtering with a trained NJ-ODE (C ABI: ``include/njode_online.h``).
 ``NJODE.forward`` is the batch form: it starts at ``t = 0`` and needs the whole record.  An
 ``OnlineState`` keeps ``(h, last_X, tau, now)`` of ``n_series`` series on the GPU; ``observe`` feeds
 the listed series their next measurement, ``predict`` reads forecasts from a copy of the state, and
-each call costs the Euler steps that are new.  The results of any sequence of calls on one series
+each call costs the Euler steps that are new.  Two kernel families serve it (``kernels=``):
+``'wave'``, one wave per series, for build-table shapes with two hidden layers and sizes up to 64
+without a GRU jump, and ``'generic'``, a tile of up to 16 series per workgroup on the matrix cores,
+for every model the shape-generic kernels run (any widths and depths, ``nn_desc = None``,
+per-network descriptions, ``use_rnn``); ``'auto'`` takes the first where it applies.  The state is
+the same: a ``state_dict`` moves between the two.  The results of any sequence of calls on one series
 are those of the reference forward on the batch that consists of that series alone, with ``times``
 equal to the targets of the calls in order.
 
@@ -21,6 +26,9 @@ import torch
 from . import _lib
 
 
+KERNELS = ('wave', 'generic', 'auto')
+
+
 def default_max_steps(t, delta_t):
     """``ceil(max(t) / delta_t) + 2``: since a clock is never negative, an upper bound of the Euler
     steps the walk to any one of the targets ``t`` takes."""
@@ -32,17 +40,36 @@ def default_max_steps(t, delta_t):
 class OnlineState:
     """The resident state of ``n_series`` series of ``model`` (``NJODE.online``)."""
 
-    def __init__(self, model, n_series, delta_t):
+    def __init__(self, model, n_series, delta_t, kernels='wave'):
         n_series, delta_t = int(n_series), float(delta_t)
         if n_series <= 0:
             raise ValueError('n_series must be positive, got {}'.format(n_series))
         if not (delta_t > 0 and math.isfinite(delta_t)):
             raise ValueError('delta_t must be positive and finite, got {!r}'.format(delta_t))
+        if kernels not in KERNELS:
+            raise ValueError('kernels must be one of {}, got {!r}'.format(KERNELS, kernels))
         self.model, self.n_series, self.delta_t = model, n_series, delta_t
         self.dims = model._get_dims()
         L = _lib.lib()
-        if not L.njode_online_supported(ctypes.byref(self.dims)):
-            raise NotImplementedError('NJODE.online: ' + L.njode_last_error().decode('utf-8', 'replace'))
+        wave_ok = bool(L.njode_online_supported(ctypes.byref(self.dims)))
+        wave_why = L.njode_last_error().decode('utf-8', 'replace')
+        if kernels == 'auto':
+            kernels = 'wave' if wave_ok else 'generic'
+        gen_ok = bool(L.njode_online_gen_supported(ctypes.byref(self.dims)))
+        gen_why = L.njode_last_error().decode('utf-8', 'replace')
+        if kernels == 'wave' and not wave_ok:
+            hint = " (kernels='generic' runs this model on the shape-generic kernels)" if gen_ok else ''
+            raise NotImplementedError('NJODE.online: ' + wave_why + hint)
+        if kernels == 'generic' and not gen_ok:
+            raise NotImplementedError('NJODE.online: ' + gen_why)
+        self.kernels = kernels
+        # generic family: series per tile of 16 chains (None: the library's rule; 1, 2, 4, 8, 16)
+        self.series_per_tile = None
+        self._tables, self._tables_stamp, self._tables_bytes = None, None, 0
+        if kernels == 'generic':
+            nbytes = ctypes.c_size_t(0)
+            _lib.check(L.njode_online_tables_bytes(ctypes.byref(self.dims), ctypes.byref(nbytes)))
+            self._tables_bytes = int(nbytes.value)
         self.d, self.H, self.d_out = model.input_size, model.hidden_size, model.output_size
         self.masked = bool(model.masked)
         dev = next(model.parameters()).device
@@ -119,7 +146,38 @@ class OnlineState:
         m._ensure_flat(full=True)
         if m._flat.device != self.device:
             raise RuntimeError('model parameters moved to {}; the state is on {}'.format(m._flat.device, self.device))
+        if self.kernels == 'generic':
+            self._spt()             # (a bad series_per_tile stops the call before its status is queued)
+            self._ensure_tables(m)
         return m._flat
+
+    def _ensure_tables(self, m):
+        """The generic family's fragment tables, packed from the flat vector at the first device
+        call and again whenever the parameters may have changed: another flat vector (address), a
+        write to it (its version counter; ``_param_writes`` for FusedAdam's raw-pointer step), or
+        a write to a parameter (the parameters' own version counters: ``load_state_dict``,
+        ``p.add_``).  A write through ``p.data`` bumps no counter and is not seen, as autograd does not
+        see it: take a new state and ``load_state_dict`` this one's."""
+        stamp = (m._flat.data_ptr(), m._flat._version, m._param_writes) + tuple(p._version for p in m._flat_params)
+        if self._tables is not None and stamp == self._tables_stamp:
+            return
+        if self._tables is None:
+            self._tables = torch.empty(self._tables_bytes, dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.lib().njode_online_tables_f32(
+            ctypes.byref(self.dims), m._flat.data_ptr(), self._tables.data_ptr(), self._tables_bytes,
+            _lib.stream_arg(self.device)))
+        self._tables_stamp = stamp
+
+    def _spt(self):
+        spt = self.series_per_tile
+        if spt is None:
+            return 0
+        if spt not in (1, 2, 4, 8, 16):
+            raise ValueError('series_per_tile must be None, 1, 2, 4, 8 or 16, got {!r}'.format(spt))
+        return int(spt)
+
+    def _gen_head(self, P):
+        return (ctypes.byref(self.dims), P.data_ptr(), self._tables.data_ptr(), self._tables_bytes)
 
     def _status(self, ids, n):
         st = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -137,6 +195,11 @@ class OnlineState:
         x = self._values(start_X, n, self.d, 'start_X')
         self._on_device()
         P, x, ids_d = self._params(), self._f32(x), self._up(ids)
+        if self.kernels == 'generic':
+            _lib.check(_lib.lib().njode_online_gen_reset_f32(
+                *self._gen_head(P), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n, x.data_ptr(),
+                self._spt(), _lib.stream_arg(self.device)))
+            return
         _lib.check(_lib.lib().njode_online_reset_f32(
             ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
             x.data_ptr(), _lib.stream_arg(self.device)))
@@ -150,6 +213,11 @@ class OnlineState:
         self._on_device()
         P, t_d, ids_d = self._params(), self._up(t), self._up(ids)
         st = self._status(ids, n)
+        if self.kernels == 'generic':
+            _lib.check(_lib.lib().njode_online_gen_advance_f32(
+                *self._gen_head(P), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n, t_d.data_ptr(),
+                self.delta_t, max_steps, self._spt(), st.data_ptr(), _lib.stream_arg(self.device)))
+            return
         _lib.check(_lib.lib().njode_online_advance_f32(
             ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
             t_d.data_ptr(), self.delta_t, max_steps, st.data_ptr(), _lib.stream_arg(self.device)))
@@ -176,6 +244,12 @@ class OnlineState:
                    torch.empty(n, self.d_out, dtype=torch.float32, device=self.device))
         yb, y = out
         st = self._status(ids, n)
+        if self.kernels == 'generic':
+            _lib.check(_lib.lib().njode_online_gen_observe_f32(
+                *self._gen_head(P), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n, t_d.data_ptr(),
+                x.data_ptr(), _lib.ptr_arg(m), self.delta_t, max_steps, self._spt(), yb.data_ptr(), y.data_ptr(),
+                st.data_ptr(), _lib.stream_arg(self.device)))
+            return yb, y
         _lib.check(_lib.lib().njode_online_observe_f32(
             ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
             t_d.data_ptr(), x.data_ptr(), _lib.ptr_arg(m), self.delta_t, max_steps, yb.data_ptr(),
@@ -200,6 +274,11 @@ class OnlineState:
         P, t_d, ids_d = self._params(), self._up(tq), self._up(ids)
         y = torch.empty(n, Q, self.d_out, dtype=torch.float32, device=self.device)
         st = self._status(ids, n)
+        if self.kernels == 'generic':
+            _lib.check(_lib.lib().njode_online_gen_predict_f32(
+                *self._gen_head(P), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n, t_d.data_ptr(), Q,
+                self.delta_t, max_steps, self._spt(), y.data_ptr(), st.data_ptr(), _lib.stream_arg(self.device)))
+            return y
         _lib.check(_lib.lib().njode_online_predict_f32(
             ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
             t_d.data_ptr(), Q, self.delta_t, max_steps, y.data_ptr(), st.data_ptr(),

@@ -1,6 +1,6 @@
 """Online filtering against what the same answer costs on the batch route.
 
-    python tools/ubench/online_bench.py [--out profiles/online_bench.jsonl]
+    python tools/ubench/online_bench.py [--out profiles/online_bench.jsonl] [--kernels generic]
 
 Per shape (demo: d = 1, H = 10, delta_t = 0.01; PhysioNet: d = H = 41, delta_t = 0.016 / 48) and
 per number of resident series N = 1, 50, 1 000, one line with
@@ -14,6 +14,13 @@ per number of resident series N = 1, 50, 1 000, one line with
 * the yardstick, code this feature does not touch: ``NJODE.get_pred`` over the series' full
   history on [0, 1] (100 Euler steps for the demo shape, 3 000 for PhysioNet), which is what an
   answer to "what do you predict now?" costs without a resident state.
+
+``--kernels generic``: the shape-generic family (``NJODE.online(..., kernels='generic')``) on the
+shapes the wave family refuses -- width 100 (d = 1, H = 10, delta_t = 0.01), the climate shape
+(d = 5, H = 50, width 400, masked; 400 grid steps of history) and ``gru_w80`` (width 80 with the GRU
+jump) -- with the same measurements; there ``step_us`` is the cost of one Euler step of a whole
+TILE (a workgroup), to be read against k_gen_fwd's 13 100 cycles per step at width 100 (DESIGN 4f);
+``tables_pack_*`` is one repack of the fragment tables, what the call after a parameter change pays.
 
 One process, warm-up calls first, medians (and the fastest call) after them.
 """
@@ -65,12 +72,24 @@ def history(shape, N):
         b = data_utils.collate_arrays(paths, obs, nb_obs, meta['dt'])
         m = models.NJODE(1, 10, 1, NN, NN, NN, False, options={'device_outputs': True})
         return m.to('cuda').eval(), b, meta['dt'], meta['maturity']
+    if shape in ('w100', 'gru_w80'):
+        w = 100 if shape == 'w100' else 80
+        nn = ((w, 'tanh'), (w, 'tanh'))
+        m, b, dt, T = history('demo', N)
+        torch.manual_seed(0)
+        m = models.NJODE(1, 10, 1, nn, nn, nn, shape == 'gru_w80', options={'device_outputs': True})
+        return m.to('cuda').eval(), b, dt, T
+    if shape == 'climate':
+        nn = ((400, 'tanh'), (400, 'tanh'))
+        b = synthetic_physionet.make_batch(batch_size=N, dim=5, n_grid=400, seed=0)
+        m = models.NJODE(5, 50, 5, nn, nn, nn, False, options={'device_outputs': True, 'masked': True})
+        return m.to('cuda').eval(), b, b['delta_t'], b['T']
     b = synthetic_physionet.make_batch(batch_size=N, n_grid=3000, seed=0)
     m = models.NJODE(41, 41, 41, NN, NN, NN, False, options={'device_outputs': True, 'masked': True})
     return m.to('cuda').eval(), b, b['delta_t'], b['T']
 
 
-def case(shape, N, reps):
+def case(shape, N, reps, kernels='wave'):
     m, b, delta_t, T = history(shape, N)
     d = b['start_X'].shape[1]
     dev = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
@@ -79,7 +98,7 @@ def case(shape, N, reps):
     def get_pred():
         return m.get_pred(dev['times'], dev['time_ptr'], dev['X'], dev['obs_idx'], delta_t, T, dev['start_X'], M=M)
 
-    st = m.online(N, delta_t)
+    st = m.online(N, delta_t, kernels=kernels)
     st.reset(dev['start_X'])
     st.replay(b['times'], b['time_ptr'], dev['X'], b['obs_idx'], M)      # a warm start from the history
     st.check()
@@ -106,10 +125,16 @@ def case(shape, N, reps):
         res['pred8'].append(timed(predict, w, reps))
         res['get_pred'].append(timed(get_pred, 2 if rnd == 0 else 0, max(reps // 8, 3)))
     st.check()
+    pack = None
+    if st.kernels == 'generic':      # what a change of the parameters costs the next call: one k_gen_pack launch
+        def repack():
+            st._tables_stamp = None
+            st._ensure_tables(m)
+        pack = timed(repack, 3, reps)
     best = {k: min(v, key=lambda r: r[0][0]) for k, v in res.items()}      # the quieter round
     g1, g30 = best['obs1'][0][0], best['obs30'][0][0]
     return {
-        'case': 'online {} N={}'.format(shape, N), 'shape': shape, 'N': N, 'delta_t': delta_t,
+        'case': 'online {} N={}'.format(shape, N), 'shape': shape, 'kernels': st.kernels, 'N': N, 'delta_t': delta_t,
         'history_euler_steps': int(round(T / delta_t)), 'history_rows': int(b['time_ptr'][-1]),
         'observe_1_step_gpu_ms_median_min': best['obs1'][0], 'observe_1_step_wall_ms_median_min': best['obs1'][1],
         'observe_30_steps_gpu_ms_median_min': best['obs30'][0],
@@ -121,6 +146,9 @@ def case(shape, N, reps):
         'get_pred_full_history_wall_ms_median_min': best['get_pred'][1],
         'get_pred_over_observe_1_step_wall': best['get_pred'][1][0] / best['obs1'][1][0],
         'both_rounds_gpu_ms_median': {k: [r[0][0] for r in v] for k, v in res.items()},
+        'tables_bytes': st._tables_bytes,
+        'tables_pack_gpu_ms_median_min': pack[0] if pack else None,
+        'tables_pack_wall_ms_median_min': pack[1] if pack else None,
     }
 
 
@@ -128,11 +156,12 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=40)
+    ap.add_argument('--kernels', default='wave', choices=('wave', 'generic'))
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU: there is nothing to measure without one'
-    for shape in ('demo', 'physionet'):
+    for shape in (('demo', 'physionet') if a.kernels == 'wave' else ('w100', 'climate', 'gru_w80')):
         for N in (1, 50, 1000):
-            line = json.dumps(case(shape, N, a.reps))
+            line = json.dumps(case(shape, N, a.reps, a.kernels))
             print(line, flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
