@@ -66,6 +66,7 @@ int njode_online_supported(const NjodeDims* dims);
  *   t       device float64 [n] (predict: [n][Q]), the targets
  *   delta_t, max_steps   the Euler step and the bound described above
  *   status  device int32 [n], every entry written: 0 reached, 1 stopped by the bound, 2 bad id
+ *           (njode_online_run_f32: 3 bad event range)
  * Every call returns NJODE_E_UNSUPPORTED for a model njode_online_supported refuses and
  * NJODE_E_BADARG -- before anything is launched -- for a null dims, params, state, state array,
  * t, status or required input, n_series <= 0, n < 0, n > n_series with ids == NULL, a delta_t that
@@ -97,6 +98,36 @@ int njode_online_predict_f32(const NjodeDims* dims, const float* params, const N
                              const int32_t* ids, int32_t n, const double* t_query, int32_t Q,
                              double delta_t, int32_t max_steps, float* Y, int32_t* status,
                              njodeStream_t stream);
+
+/* A run of events per series in one launch.  Events are laid out BY SERIES (CSR): row r of the call
+ * owns events ev_ptr[r] .. ev_ptr[r + 1] - 1 and applies them, in that order, to series ids[r].
+ *   ev_ptr   device int32 [n + 1]
+ *   n_events rows of t, X, M, kind, Y_before and Y, >= 0 (0: every range is empty; t, X, M may be NULL)
+ *   t        device float64 [n_events]; the times of a series need not ascend (a jump at t <= now takes
+ *            no step)
+ *   X, M     device fp32 [n_events][input_size] (M: masked models only, else NULL)
+ *   kind     device int32 [n_events] or NULL (all 1).  1: an observation, exactly
+ *            njode_online_observe_f32 at t[e].  0: an empty slice, exactly njode_online_advance_f32
+ *            at t[e]; its rows of X / M are never read, and Y_before[e] and Y[e] both receive the
+ *            readout of the state it arrives at (what njode_online_predict_f32 with Q = 1 at t[e]
+ *            would have returned before the call).
+ *   Y_before, Y   device fp32 [n_events][output_size], each may be NULL
+ *   n_done   device int32 [n], every entry written: the events of the row that were applied
+ * The result of a run on a series -- the state after it and every output row -- is, in bits, the
+ * result of the same events fed one call at a time.  max_steps bounds the step loop in front of EACH
+ * event's target.  A series the bound stops at its event k keeps the state it reached, applies no jump
+ * at k and skips its remaining events: rows k .. end of its range of Y_before / Y are NaN, status 1,
+ * n_done = k.  Otherwise status 0 and n_done = the length of the range.  An id outside the state:
+ * status 2, n_done 0, nothing touched.  A range that does not satisfy
+ * 0 <= ev_ptr[r] <= ev_ptr[r + 1] <= n_events: status 3, n_done 0; no event is read, nothing of the
+ * state is touched and no output row written.  Every loop is counted: events by the checked range,
+ * steps by max_steps.  NJODE_E_BADARG as for observe, and for a null ev_ptr or n_done, n_events < 0,
+ * and n_events > 0 with a null t or X (masked: or M). */
+int njode_online_run_f32(const NjodeDims* dims, const float* params, const NjodeOnlineState* state,
+                         const int32_t* ids, int32_t n, const int32_t* ev_ptr, int32_t n_events,
+                         const double* t, const float* X, const float* M, const int32_t* kind,
+                         double delta_t, int32_t max_steps, float* Y_before, float* Y, int32_t* status,
+                         int32_t* n_done, njodeStream_t stream);
 
 /* ---- The same calls on the shape-generic matrix-core kernels --------------------------------------
  * For the models njode_online_supported refuses: any sizes within the envelope of njode_supported's
@@ -150,6 +181,15 @@ int njode_online_gen_predict_f32(const NjodeDims* dims, const float* params, con
                                  int32_t n, const double* t_query, int32_t Q, double delta_t,
                                  int32_t max_steps, int32_t series_per_tile, float* Y, int32_t* status,
                                  njodeStream_t stream);
+
+/* njode_online_run_f32 on this family: a tile runs as many rounds as its longest range has events;
+ * a chain whose range is exhausted idles. */
+int njode_online_gen_run_f32(const NjodeDims* dims, const float* params, const void* tables,
+                             size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                             int32_t n, const int32_t* ev_ptr, int32_t n_events, const double* t,
+                             const float* X, const float* M, const int32_t* kind, double delta_t,
+                             int32_t max_steps, int32_t series_per_tile, float* Y_before, float* Y,
+                             int32_t* status, int32_t* n_done, njodeStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -45,10 +45,10 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_records_val_fill',
            # include/njode_online.h
            'njode_online_supported', 'njode_online_reset_f32', 'njode_online_advance_f32',
-           'njode_online_observe_f32', 'njode_online_predict_f32',
+           'njode_online_observe_f32', 'njode_online_predict_f32', 'njode_online_run_f32',
            'njode_online_gen_supported', 'njode_online_tables_bytes', 'njode_online_tables_f32',
            'njode_online_gen_reset_f32', 'njode_online_gen_advance_f32', 'njode_online_gen_observe_f32',
-           'njode_online_gen_predict_f32',
+           'njode_online_gen_predict_f32', 'njode_online_gen_run_f32',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -263,6 +263,7 @@ def lib():
     L.njode_online_advance_f32.argtypes = [dp, vp, sp, vp, i32, vp, f64, i32, vp, vp]
     L.njode_online_observe_f32.argtypes = [dp, vp, sp, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp]
     L.njode_online_predict_f32.argtypes = [dp, vp, sp, vp, i32, vp, i32, f64, i32, vp, vp, vp]
+    L.njode_online_run_f32.argtypes = [dp, vp, sp, vp, i32, vp, i32, vp, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp]
     # the generic family: (dims, params, tables, tables_bytes, state, ids, n, ..., series_per_tile, ..., stream)
     L.njode_online_gen_supported.argtypes = [dp]
     L.njode_online_tables_bytes.argtypes = [dp, C.POINTER(sz)]
@@ -272,10 +273,13 @@ def lib():
     L.njode_online_gen_observe_f32.argtypes = [dp, vp, vp, sz, sp, vp, i32, vp, vp, vp, f64, i32, i32, vp, vp,
                                                vp, vp]
     L.njode_online_gen_predict_f32.argtypes = [dp, vp, vp, sz, sp, vp, i32, vp, i32, f64, i32, i32, vp, vp, vp]
+    L.njode_online_gen_run_f32.argtypes = [dp, vp, vp, sz, sp, vp, i32, vp, i32, vp, vp, vp, vp, f64, i32, i32, vp,
+                                           vp, vp, vp, vp]
     for name in ('njode_online_supported', 'njode_online_reset_f32', 'njode_online_advance_f32',
                  'njode_online_observe_f32', 'njode_online_predict_f32', 'njode_online_gen_supported',
                  'njode_online_tables_bytes', 'njode_online_tables_f32', 'njode_online_gen_reset_f32',
-                 'njode_online_gen_advance_f32', 'njode_online_gen_observe_f32', 'njode_online_gen_predict_f32'):
+                 'njode_online_gen_advance_f32', 'njode_online_gen_observe_f32', 'njode_online_gen_predict_f32',
+                 'njode_online_run_f32', 'njode_online_gen_run_f32'):
         getattr(L, name).restype = C.c_int
     L.njode_selftest_dropout_words.argtypes = [u64, u64, C.c_uint32, C.c_uint32, i32, vp, vp]
     L.njode_selftest_dropout_words.restype = C.c_int

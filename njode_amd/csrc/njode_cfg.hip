@@ -592,6 +592,7 @@ template <class CC> static hipError_t online_launch(const OnlineArgs& a, int mod
     if (mode == ONLINE_ADVANCE) k_online<CC, ONLINE_ADVANCE><<<grid, block, 0, st>>>(a);
     else if (mode == ONLINE_OBSERVE) k_online<CC, ONLINE_OBSERVE><<<grid, block, 0, st>>>(a);
     else if (mode == ONLINE_PREDICT) k_online<CC, ONLINE_PREDICT><<<grid, block, 0, st>>>(a);
+    else if (mode == ONLINE_RUN) k_online<CC, ONLINE_RUN><<<grid, block, 0, st>>>(a);
     else k_online<CC, ONLINE_RESET><<<grid, block, 0, st>>>(a);
     return hipGetLastError();
   } else {

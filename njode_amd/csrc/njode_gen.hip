@@ -874,6 +874,21 @@ extern "C" int njode_online_gen_predict_f32(const NjodeDims* dims, const float* 
   return online_launch(m, tables, a, ONLINE_PREDICT, series_per_tile, stream);
 }
 
+extern "C" int njode_online_gen_run_f32(const NjodeDims* dims, const float* params, const void* tables,
+                                        size_t tables_bytes, const NjodeOnlineState* state, const int32_t* ids,
+                                        int32_t n, const int32_t* ev_ptr, int32_t n_events, const double* t,
+                                        const float* X, const float* M, const int32_t* kind, double delta_t,
+                                        int32_t max_steps, int32_t series_per_tile, float* Y_before, float* Y,
+                                        int32_t* status, int32_t* n_done, njodeStream_t stream) {
+  Model m;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, tables, tables_bytes, state, ids, n, series_per_tile, m, &a)) return rc;
+  if (int rc = online_events(delta_t, max_steps, m.a.masked != 0, ev_ptr, n_events, t, X, M, kind, Y_before, Y, status,
+                             n_done, &a))
+    return rc;
+  return online_launch(m, tables, a, ONLINE_RUN, series_per_tile, stream);
+}
+
 #ifdef NJ_GEN_STAMPS
 // diagnostic build only: read and clear the phase stamps of njode_gen.h
 extern "C" int njode_gen_debug_stamps(unsigned long long* out16) {

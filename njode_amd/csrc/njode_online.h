@@ -12,9 +12,15 @@
 // at most max_steps steps in front of one target, whatever the inputs hold; a series the bound stops
 // keeps the state it reached (no jump, no readout) and reports status 1.
 //
-// One body, four modes (OnlineMode): advance (1 target, no jump, state written), observe (1 target,
+// One body, five modes (OnlineMode): advance (1 target, no jump, state written), observe (1 target,
 // jump, readouts before and after it, state written), predict (Q targets, a readout at each, on a
-// register copy of the state: nothing written back), reset (h = encoder(start_X, mask 0)).
+// register copy of the state: nothing written back), reset (h = encoder(start_X, mask 0)), run (the
+// row's range of events ev_ptr[row] .. ev_ptr[row + 1] - 1 in order, each an observe (kind 1) or an
+// advance with a readout (kind 0), around the state in registers: the ODE rows are loaded and the
+// tables filled once, the state is written once, at the end or where the bound stopped the series).
+// A run leaves the bits of the single calls: between two calls h, last_X and tau pass through fp32
+// memory unchanged and th, c1 are functions of them, so after a jump the run takes th = tanh_f(h_new)
+// and c1 = segment_c1(tanh_f(last_X_new), tau_new) from the same functions.
 //
 // Residual cases: every one of FFNN (models.py:240-259), not only the identity ChainOk admits --
 // case 1 with out = m in: y[o] += x[o % in], case 2 with in = m out: y[o] += mean_c x[c out + o]; the
@@ -102,6 +108,13 @@ template <int NK> NJ_DEV float online_dot_lds(lfp tab_lane, const float (&R)[4],
 
 // a value every lane holds alike, as a scalar condition
 NJ_DEV bool online_uniform(bool v) { return __builtin_amdgcn_readfirstlane(v ? 1 : 0) != 0; }
+// ... and a float64 every lane holds alike, as a scalar (the bits are untouched)
+NJ_DEV double online_uniform_f64(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 template <class C, int MODE>
 __global__ void __launch_bounds__(64 * ONLINE_WAVES) k_online(OnlineArgs a) {
@@ -110,7 +123,8 @@ __global__ void __launch_bounds__(64 * ONLINE_WAVES) k_online(OnlineArgs a) {
   using ND = typename C::Dec;
   using L = ChainLds<C>;
   constexpr int D = C::D, H = C::H, DO = C::DO, W = C::W, EIN = C::ENC_IN, OIN = C::ODE_IN;
-  constexpr bool JUMP = MODE == ONLINE_OBSERVE, RESET = MODE == ONLINE_RESET;
+  constexpr bool RUN = MODE == ONLINE_RUN;
+  constexpr bool JUMP = MODE == ONLINE_OBSERVE || RUN, RESET = MODE == ONLINE_RESET;
   constexpr bool NEED_ENC = JUMP || RESET, NEED_DEC = JUMP || MODE == ONLINE_PREDICT;
   __shared__ __attribute__((aligned(16))) float lds_raw[L::FWD_FLOATS];
   __shared__ float scr_raw[64 * ONLINE_WAVES];
@@ -143,7 +157,20 @@ __global__ void __launch_bounds__(64 * ONLINE_WAVES) k_online(OnlineArgs a) {
   const int sid = __builtin_amdgcn_readfirstlane(a.ids ? a.ids[row] : row);
   if (sid < 0 || sid >= a.n_series) {   // (nothing of the state is touched through such an id)
     if (!RESET && lane == 0) a.status[row] = 2;
+    if (RUN && lane == 0) a.n_done[row] = 0;
     return;
+  }
+  [[maybe_unused]] int ev0 = 0, ev1 = 0;   // run: the row's events (wave-uniform); a range outside the call reads none
+  if constexpr (RUN) {
+    ev0 = __builtin_amdgcn_readfirstlane(a.ev_ptr[row]);
+    ev1 = __builtin_amdgcn_readfirstlane(a.ev_ptr[row + 1]);
+    if (ev0 < 0 || ev1 < ev0 || ev1 > a.n_events) {
+      if (lane == 0) {
+        a.status[row] = 3;
+        a.n_done[row] = 0;
+      }
+      return;
+    }
   }
 
   lfp tE1 = T + L::FE1 + lane * 4, tE1M = T + L::FE1M + lane * 4, tE2 = T + L::FE2 + lane * 4,
@@ -224,7 +251,7 @@ __global__ void __launch_bounds__(64 * ONLINE_WAVES) k_online(OnlineArgs a) {
     const float xl = uD ? *st_x : 0.0f;
     float tau = a.tau[sid];
     double now = a.now[sid];
-    const float c1 = segment_c1(uD ? tanh_f(xl) : 0.0f, tau);
+    float c1 = segment_c1(uD ? tanh_f(xl) : 0.0f, tau);
 
     // Euler step (models.py:369-377, 430-445) of length dt from the clock value t
     auto euler_step = [&](float dt, float t) {
@@ -268,33 +295,76 @@ __global__ void __launch_bounds__(64 * ONLINE_WAVES) k_online(OnlineArgs a) {
       }
       if (lane == 0) a.status[row] = ok ? 0 : 1;
     } else {
-      const double target = a.t[row];
-      const bool ok = walk(target);
-      if constexpr (JUMP) {
-        float* const yb_p = a.Y_before ? a.Y_before + (size_t)row * DO + jO : nullptr;
-        float* const y_p = a.Y ? a.Y + (size_t)row * DO + jO : nullptr;
-        if (ok) {   // the jump (models.py:457-489)
+      // the jump (models.py:457-489) with row `r` of X / M; the new last_X of the own unit
+      [[maybe_unused]] auto jump = [&](float ybj, size_t r, float& yn) {
+        const float x = uD ? a.X[r * D + jD] : 0.0f;
+        const float m = (C::MASKED && uD) ? a.M[r * D + jD] : 0.0f;
+        const float xin = C::MASKED ? x * m + (1.0f - m) * ybj : x;
+        const float hn = encode(xin, uD ? tanh_f(xin) : 0.0f, m);
+        const float thn = uH ? tanh_f(hn) : 0.0f;
+        yn = readout(hn, thn);
+        h = hn;
+        th = thn;
+        return C::MASKED ? yn : x;
+      };
+      if constexpr (RUN) {
+        // the row's events in order around the register state; e, the kinds and the targets are scalars
+        bool ok = true, jumped = false;
+        float xnew = xl;
+        int e = ev0;
+        for (; e < ev1; ++e) {
+          const double target = online_uniform_f64(a.t[e]);
+          const int kd = a.kind ? __builtin_amdgcn_readfirstlane(a.kind[e]) : 1;
+          ok = walk(target);
+          if (!ok) break;
           const float ybj = readout(h, th);
-          const float x = uD ? a.X[(size_t)row * D + jD] : 0.0f;
-          const float m = (C::MASKED && uD) ? a.M[(size_t)row * D + jD] : 0.0f;
-          const float xin = C::MASKED ? x * m + (1.0f - m) * ybj : x;
-          const float hn = encode(xin, uD ? tanh_f(xin) : 0.0f, m);
-          const float thn = uH ? tanh_f(hn) : 0.0f;
-          const float yn = readout(hn, thn);
-          if (uO && yb_p) *yb_p = ybj;
-          if (uO && y_p) *y_p = yn;
-          h = hn;
-          if (uD) *st_x = C::MASKED ? yn : x;
-          if (lane == 0) a.tau[sid] = (float)target;
-        } else {
-          if (uO && yb_p) *yb_p = qnan;
-          if (uO && y_p) *y_p = qnan;
+          float yn = ybj;   // (an empty slice: the readout of the state it arrives at, twice)
+          if (kd != 0) {
+            xnew = jump(ybj, (size_t)e, yn);
+            tau = (float)target;
+            c1 = segment_c1(uD ? tanh_f(xnew) : 0.0f, tau);
+            jumped = true;
+          }
+          if (uO && a.Y_before) a.Y_before[(size_t)e * DO + jO] = ybj;
+          if (uO && a.Y) a.Y[(size_t)e * DO + jO] = yn;
         }
-      }
-      if (uH) *st_h = h;
-      if (lane == 0) {
-        a.now[sid] = now;
-        a.status[row] = ok ? 0 : 1;
+        const int done = e - ev0;
+        for (; e < ev1; ++e) {   // the event the bound stopped the series at, and those behind it
+          if (uO && a.Y_before) a.Y_before[(size_t)e * DO + jO] = qnan;
+          if (uO && a.Y) a.Y[(size_t)e * DO + jO] = qnan;
+        }
+        if (uH) *st_h = h;
+        if (jumped && uD) *st_x = xnew;
+        if (lane == 0) {
+          if (jumped) a.tau[sid] = tau;
+          a.now[sid] = now;
+          a.status[row] = ok ? 0 : 1;
+          a.n_done[row] = done;
+        }
+      } else {
+        const double target = a.t[row];
+        const bool ok = walk(target);
+        if constexpr (JUMP) {
+          float* const yb_p = a.Y_before ? a.Y_before + (size_t)row * DO + jO : nullptr;
+          float* const y_p = a.Y ? a.Y + (size_t)row * DO + jO : nullptr;
+          if (ok) {
+            const float ybj = readout(h, th);
+            float yn;
+            const float xnew = jump(ybj, (size_t)row, yn);
+            if (uO && yb_p) *yb_p = ybj;
+            if (uO && y_p) *y_p = yn;
+            if (uD) *st_x = xnew;
+            if (lane == 0) a.tau[sid] = (float)target;
+          } else {
+            if (uO && yb_p) *yb_p = qnan;
+            if (uO && y_p) *y_p = qnan;
+          }
+        }
+        if (uH) *st_h = h;
+        if (lane == 0) {
+          a.now[sid] = now;
+          a.status[row] = ok ? 0 : 1;
+        }
       }
     }
   }

@@ -150,3 +150,17 @@ extern "C" int njode_online_predict_f32(const NjodeDims* dims, const float* para
   a.status = status;
   return online_run(ops, a, ONLINE_PREDICT, stream);
 }
+
+extern "C" int njode_online_run_f32(const NjodeDims* dims, const float* params, const NjodeOnlineState* state,
+                                    const int32_t* ids, int32_t n, const int32_t* ev_ptr, int32_t n_events,
+                                    const double* t, const float* X, const float* M, const int32_t* kind,
+                                    double delta_t, int32_t max_steps, float* Y_before, float* Y, int32_t* status,
+                                    int32_t* n_done, njodeStream_t stream) {
+  const OnlineOps* ops;
+  OnlineArgs a;
+  if (int rc = online_common(dims, params, state, ids, n, &ops, &a)) return rc;
+  if (int rc = online_events(delta_t, max_steps, (dims->flags & NJODE_F_MASKED) != 0, ev_ptr, n_events, t, X, M, kind,
+                             Y_before, Y, status, n_done, &a))
+    return rc;
+  return online_run(ops, a, ONLINE_RUN, stream);
+}

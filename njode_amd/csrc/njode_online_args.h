@@ -8,7 +8,7 @@
 
 namespace njode {
 
-enum OnlineMode { ONLINE_ADVANCE = 0, ONLINE_OBSERVE = 1, ONLINE_PREDICT = 2, ONLINE_RESET = 3 };
+enum OnlineMode { ONLINE_ADVANCE = 0, ONLINE_OBSERVE = 1, ONLINE_PREDICT = 2, ONLINE_RESET = 3, ONLINE_RUN = 4 };
 constexpr int ONLINE_WAVES = 8;   // waves per block; the first `spb` of them own a series each
 
 struct OnlineArgs {
@@ -29,7 +29,12 @@ struct OnlineArgs {
   int max_steps;          // bound of the step loop in front of ONE target
   float* Y_before;        // [n][DO] observe, nullable
   float* Y;               // [n][DO] observe (nullable) | [n][Q][DO] predict
-  int* status;            // [n]: 0 reached, 1 the bound stopped it, 2 id outside the state
+  int* status;            // [n]: 0 reached, 1 the bound stopped it, 2 id outside the state, 3 bad event range
+  // run: events by series (CSR); t, X, M, Y_before, Y are then [n_events] rows, indexed by event
+  const int* ev_ptr;      // [n + 1] row r owns events ev_ptr[r] .. ev_ptr[r + 1] - 1
+  int n_events;
+  const int* kind;        // [n_events] 1 observation, 0 empty slice; null: all observations
+  int* n_done;            // [n] events of the row that were applied
   int spb;                // series per block, 1 .. ONLINE_WAVES
 };
 

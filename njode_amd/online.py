@@ -4,7 +4,10 @@ Online filtering with a trained NJ-ODE (C ABI: ``include/njode_online.h``).
 ``NJODE.forward`` is the batch form: it starts at ``t = 0`` and needs the whole record.  An
 ``OnlineState`` keeps ``(h, last_X, tau, now)`` of ``n_series`` series on the GPU; ``observe`` feeds
 the listed series their next measurement, ``predict`` reads forecasts from a copy of the state, and
-each call costs the Euler steps that are new.  Two kernel families serve it (``kernels=``):
+each call costs the Euler steps that are new; ``observe_many`` applies a run of events per series --
+observations and empty slices, laid out by series -- in ONE launch, with the bits of the same events
+fed one call at a time, and ``replay(fused=True)`` is the warm start from a collated history through
+it.  Two kernel families serve it (``kernels=``):
 ``'wave'``, one wave per series, for build-table shapes with two hidden layers and sizes up to 64
 without a GRU jump, and ``'generic'``, a tile of up to 16 series per workgroup on the matrix cores,
 for every model the shape-generic kernels run (any widths and depths, ``nn_desc = None``,
@@ -35,6 +38,26 @@ def default_max_steps(t, delta_t):
     t = np.asarray(t, dtype=np.float64)
     top = float(t.max()) if t.size else 0.0
     return max(int(math.ceil(top / float(delta_t))) + 2, 1)
+
+
+def by_series(time_ptr, obs_idx):
+    """The rows of a collated batch (``time_ptr``: the rows of each time slice, ``obs_idx``: the
+    series of each row) laid out by series: ``(ids, ev_ptr, perm, inv)``.  ``ids`` are the series
+    that have rows, ascending; series ``ids[r]`` owns the sorted rows ``ev_ptr[r] .. ev_ptr[r + 1] - 1``;
+    sorted row ``k`` is row ``perm[k]`` of the batch and row ``i`` of the batch is sorted row
+    ``inv[i]``.  The sort is stable, so a series keeps the order of its rows, which is that of the
+    slices.  A pure host function."""
+    ptr = np.asarray(time_ptr, dtype=np.int64)
+    idx = np.asarray(obs_idx, dtype=np.int64)
+    if ptr.ndim != 1 or ptr.size < 1 or idx.ndim != 1 or ptr[0] != 0 or ptr[-1] != idx.size or np.any(np.diff(ptr) < 0):
+        raise ValueError('time_ptr does not describe {} slices of {} rows'.format(max(ptr.size - 1, 0), idx.size))
+    perm = np.argsort(idx, kind='stable').astype(np.int64)
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.size, dtype=np.int64)
+    ids, counts = np.unique(idx, return_counts=True)
+    ev_ptr = np.zeros(ids.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=ev_ptr[1:])
+    return ids.astype(np.int64), ev_ptr, perm, inv
 
 
 class OnlineState:
@@ -79,6 +102,7 @@ class OnlineState:
         self.tau = torch.zeros(n_series, dtype=torch.float32, device=dev)
         self.now = torch.zeros(n_series, dtype=torch.float64, device=dev)
         self.status = None      # the status tensor of the last advance / observe / predict call
+        self.n_done = None      # observe_many: the events applied per row of the last call
         self._pending = []      # (ids, status tensor) of the calls check() has not read yet
 
     # -- host-side checks ---------------------------------------------------------------
@@ -181,7 +205,7 @@ class OnlineState:
 
     def _status(self, ids, n):
         st = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.status = st        # the last call's: one entry per row, 0 reached / 1 bound / 2 bad id
+        self.status = st        # the last call's: one entry per row, 0 reached / 1 bound / 2 bad id / 3 bad range
         self._pending.append((np.arange(n) if ids is None else ids.copy(), st))
         if len(self._pending) > 256:
             self.check()
@@ -285,10 +309,72 @@ class OnlineState:
             _lib.stream_arg(self.device)))
         return y
 
-    def replay(self, times, time_ptr, X, obs_idx, M=None):
+    def observe_many(self, ev_ptr, t, X, M=None, kind=None, ids=None, max_steps=None, out=None):
+        """A run of events per listed series in one launch.  Events are laid out by series: row
+        ``r`` of the call owns events ``ev_ptr[r] .. ev_ptr[r + 1] - 1`` and applies them in that
+        order.  ``kind[e] = 1`` (or ``kind=None``) is ``observe`` at ``t[e]`` with ``X[e]`` (``M[e]``);
+        ``kind[e] = 0`` is ``advance`` to ``t[e]``, and both its output rows are the readout of the
+        state it arrives at.  Returns ``(Y_before, Y)``, ``[n_events, d_out]`` each, and leaves the
+        events applied per row in ``self.n_done`` beside ``self.status``.  The results are the bits
+        of the same events fed one call at a time; ``max_steps`` bounds the steps in front of each
+        event, and a series it stops skips its remaining events (their rows are NaN)."""
+        self._eval_only()
+        raw = np.asarray(ev_ptr)
+        if raw.ndim != 1 or raw.size < 1 or not np.issubdtype(raw.dtype, np.integer):
+            raise ValueError('ev_ptr must be a flat list of integers, one more than rows')
+        ids, n = self._ids(ids, raw.size - 1)
+        ptr = raw.astype(np.int64)
+        n_events = int(np.shape(t)[0]) if np.ndim(t) else -1
+        if ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != n_events:
+            raise ValueError('ev_ptr does not describe {} ranges of {} events'.format(n, n_events))
+        if n_events >= 2 ** 31:
+            raise ValueError('{} events in one call'.format(n_events))
+        t = self._times(t, (n_events,))
+        x = self._values(X, n_events, self.d, 'X')
+        if self.masked and M is None:
+            raise ValueError('a masked model needs M')
+        if not self.masked and M is not None:
+            raise ValueError('M given to an unmasked model')
+        m = self._values(M, n_events, self.d, 'M') if self.masked else None
+        if kind is not None:
+            kraw = np.asarray(kind)
+            if kraw.shape != (n_events,) or (kraw.size and not (np.issubdtype(kraw.dtype, np.integer)
+                                                                 or kraw.dtype == np.bool_)):
+                raise ValueError('kind must be {} integers'.format(n_events))
+            if kraw.size and not np.all((kraw == 0) | (kraw == 1)):
+                raise ValueError('kind entries must be 0 (empty slice) or 1 (observation)')
+            kind = np.ascontiguousarray(kraw.astype(np.int32))
+        max_steps = default_max_steps(t, self.delta_t) if max_steps is None else int(max_steps)
+        self._on_device()
+        P, t_d, ids_d, x = self._params(), self._up(t), self._up(ids), self._f32(x)
+        ptr_d, kind_d = self._up(ptr.astype(np.int32)), self._up(kind)
+        m = self._f32(m) if m is not None else None
+        if out is None:
+            out = (torch.empty(n_events, self.d_out, dtype=torch.float32, device=self.device),
+                   torch.empty(n_events, self.d_out, dtype=torch.float32, device=self.device))
+        yb, y = out
+        st = self._status(ids, n)
+        self.n_done = torch.empty(n, dtype=torch.int32, device=self.device)
+        if self.kernels == 'generic':
+            _lib.check(_lib.lib().njode_online_gen_run_f32(
+                *self._gen_head(P), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n, ptr_d.data_ptr(), n_events,
+                t_d.data_ptr(), x.data_ptr(), _lib.ptr_arg(m), _lib.ptr_arg(kind_d), self.delta_t, max_steps,
+                self._spt(), yb.data_ptr(), y.data_ptr(), st.data_ptr(), self.n_done.data_ptr(),
+                _lib.stream_arg(self.device)))
+            return yb, y
+        _lib.check(_lib.lib().njode_online_run_f32(
+            ctypes.byref(self.dims), P.data_ptr(), ctypes.byref(self._struct()), _lib.ptr_arg(ids_d), n,
+            ptr_d.data_ptr(), n_events, t_d.data_ptr(), x.data_ptr(), _lib.ptr_arg(m), _lib.ptr_arg(kind_d),
+            self.delta_t, max_steps, yb.data_ptr(), y.data_ptr(), st.data_ptr(), self.n_done.data_ptr(),
+            _lib.stream_arg(self.device)))
+        return yb, y
+
+    def replay(self, times, time_ptr, X, obs_idx, M=None, fused=False):
         """Feed a collated batch slice by slice (``obs_idx``: the series of each row): a warm start
         from history.  A slice without rows moves nobody.  Returns ``(Y_before, Y)``, one row per
-        row of ``X``."""
+        row of ``X``.  ``fused=True``: the rows are sorted by series on the host (stable: a series
+        keeps its time order) and fed as ONE ``observe_many`` to the series that have rows; the
+        results, in the original row order, are the bits of the loop's."""
         self._eval_only()
         times = np.asarray(times, dtype=np.float64)
         ptr = np.asarray(time_ptr, dtype=np.int64)
@@ -301,6 +387,14 @@ class OnlineState:
         if not self.masked and M is not None:
             raise ValueError('M given to an unmasked model')
         m = self._values(M, idx.size, self.d, 'M') if self.masked else None
+        if fused:
+            ids, ev_ptr, perm, inv = by_series(ptr, idx)
+            t_row = np.repeat(times, np.diff(ptr))[perm]
+            sel = torch.from_numpy(perm).to(x.device)
+            msel = None if m is None else m[torch.from_numpy(perm).to(m.device)]
+            yb, y = self.observe_many(ev_ptr, t_row, x[sel], msel, ids=ids)
+            back = torch.from_numpy(inv).to(self.device)
+            return yb[back], y[back]
         self._on_device()
         x = self._f32(x)
         m = self._f32(m) if m is not None else None
@@ -318,13 +412,16 @@ class OnlineState:
         """Read the status of every call since the last check (synchronises); ``RuntimeError`` naming
         the series that the step bound stopped."""
         pending, self._pending = self._pending, []
-        stopped, bad = set(), set()
+        stopped, bad, ranges = set(), set(), set()
         for ids, st in pending:
             s = st.cpu().numpy()
             stopped.update(int(i) for i in ids[s == 1])
             bad.update(int(i) for i in ids[s == 2])
+            ranges.update(int(i) for i in ids[s == 3])
         if bad:
             raise RuntimeError('online: ids outside the state: {}'.format(sorted(bad)))
+        if ranges:
+            raise RuntimeError('online: series {} were given a range of events outside the call'.format(sorted(ranges)))
         if stopped:
             raise RuntimeError('online: series {} hit max_steps before their target; their state is where '
                                'the bound stopped them'.format(sorted(stopped)))

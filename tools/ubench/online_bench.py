@@ -22,6 +22,11 @@ jump) -- with the same measurements; there ``step_us`` is the cost of one Euler 
 TILE (a workgroup), to be read against k_gen_fwd's 13 100 cycles per step at width 100 (DESIGN 4f);
 ``tables_pack_*`` is one repack of the fragment tables, what the call after a parameter change pays.
 
+``--run``: runs of events (``observe_many``) instead.  Per shape and N, K = 8 and K = 64 observations
+per series, one Euler step apart, as ONE ``observe_many`` against K ``observe`` calls in the same
+process (HIP events and wall clock, as above), and the warm start from the shape's history:
+``reset`` + ``replay(fused=True)`` against ``reset`` + ``replay()`` against ``get_pred``.
+
 One process, warm-up calls first, medians (and the fastest call) after them.
 """
 import argparse
@@ -152,16 +157,89 @@ def case(shape, N, reps, kernels='wave'):
     }
 
 
+def run_case(shape, N, reps, kernels='wave'):
+    m, b, delta_t, T = history(shape, N)
+    d = b['start_X'].shape[1]
+    dev = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
+    M = dev.get('M')
+
+    def get_pred():
+        return m.get_pred(dev['times'], dev['time_ptr'], dev['X'], dev['obs_idx'], delta_t, T, dev['start_X'], M=M)
+
+    st = m.online(N, delta_t, kernels=kernels)
+
+    def warm_start(fused):
+        def fn():
+            st.reset(dev['start_X'])
+            st.replay(b['times'], b['time_ptr'], dev['X'], b['obs_idx'], M, fused=fused)
+        return fn
+
+    few = max(reps // 8, 3)
+    res = {'replay_loop': [], 'replay_fused': [], 'get_pred': []}
+    for rnd in range(2):
+        w = 1 if rnd == 0 else 0
+        res['replay_fused'].append(timed(warm_start(True), w, few))
+        res['replay_loop'].append(timed(warm_start(False), w, few))
+        res['get_pred'].append(timed(get_pred, 2 * w, few))
+    st.check()
+    clock = {'t': float(T)}
+    out = {}
+    for K in (8, 64):
+        X = torch.rand(N * K, d, device='cuda')
+        Mo = (torch.rand(N * K, d, device='cuda') < 0.15).float() if M is not None else None
+        Xs = X.view(N, K, d).transpose(0, 1).contiguous()        # [K][N][d]: call k of the loop
+        Ms = Mo.view(N, K, d).transpose(0, 1).contiguous() if Mo is not None else None
+        ev_ptr = np.arange(N + 1) * K
+
+        def one_run():
+            t = clock['t'] + delta_t * np.arange(1, K + 1)
+            clock['t'] = float(t[-1])
+            st.observe_many(ev_ptr, np.tile(t, N), X, Mo)
+
+        def k_calls():
+            for k in range(K):
+                clock['t'] += delta_t
+                st.observe(np.full(N, clock['t']), Xs[k], None if Ms is None else Ms[k])
+
+        r = {'run': [], 'calls': []}
+        for rnd in range(2):
+            w = 3 if rnd == 0 else 0
+            r['run'].append(timed(one_run, w, reps))
+            r['calls'].append(timed(k_calls, w, max(reps // 4, 3)))
+        st.check()
+        best = {k: min(v, key=lambda x: x[0][0]) for k, v in r.items()}
+        out['run_k{}_gpu_ms_median_min'.format(K)] = best['run'][0]
+        out['run_k{}_wall_ms_median_min'.format(K)] = best['run'][1]
+        out['calls_k{}_gpu_ms_median_min'.format(K)] = best['calls'][0]
+        out['calls_k{}_wall_ms_median_min'.format(K)] = best['calls'][1]
+        out['calls_over_run_k{}_wall'.format(K)] = best['calls'][1][0] / best['run'][1][0]
+    best = {k: min(v, key=lambda x: x[0][0]) for k, v in res.items()}
+    out.update({
+        'case': 'online run {} N={}'.format(shape, N), 'shape': shape, 'kernels': st.kernels, 'N': N, 'delta_t': delta_t,
+        'history_euler_steps': int(round(T / delta_t)), 'history_rows': int(b['time_ptr'][-1]),
+        'history_slices_with_rows': int(np.count_nonzero(np.diff(np.asarray(b['time_ptr'])))),
+        'replay_loop_gpu_ms_median_min': best['replay_loop'][0], 'replay_loop_wall_ms_median_min': best['replay_loop'][1],
+        'replay_fused_gpu_ms_median_min': best['replay_fused'][0],
+        'replay_fused_wall_ms_median_min': best['replay_fused'][1],
+        'get_pred_full_history_gpu_ms_median_min': best['get_pred'][0],
+        'get_pred_full_history_wall_ms_median_min': best['get_pred'][1],
+        'replay_loop_over_fused_wall': best['replay_loop'][1][0] / best['replay_fused'][1][0],
+        'replay_fused_over_get_pred_wall': best['replay_fused'][1][0] / best['get_pred'][1][0],
+    })
+    return out
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--run', action='store_true', help='measure runs of events (observe_many, fused replay)')
     ap.add_argument('--reps', type=int, default=40)
     ap.add_argument('--kernels', default='wave', choices=('wave', 'generic'))
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU: there is nothing to measure without one'
     for shape in (('demo', 'physionet') if a.kernels == 'wave' else ('w100', 'climate', 'gru_w80')):
         for N in (1, 50, 1000):
-            line = json.dumps(case(shape, N, a.reps, a.kernels))
+            line = json.dumps((run_case if a.run else case)(shape, N, a.reps, a.kernels))
             print(line, flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
