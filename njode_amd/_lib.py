@@ -49,6 +49,8 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_online_gen_supported', 'njode_online_tables_bytes', 'njode_online_tables_f32',
            'njode_online_gen_reset_f32', 'njode_online_gen_advance_f32', 'njode_online_gen_observe_f32',
            'njode_online_gen_predict_f32', 'njode_online_gen_run_f32',
+           # include/njode_f64.h
+           'njode_f64_supported', 'njode_f64_workspace_bytes', 'njode_forward_f64', 'njode_backward_f64',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -87,6 +89,18 @@ class NjodeBatch(C.Structure):
                 ('obs_idx', C.c_void_p), ('n_obs_ot', C.c_void_p),
                 ('loss_batch_size', C.c_float), ('path_id_offset', C.c_int64),
                 ('plan', C.c_void_p), ('grad_hT', C.c_void_p)]
+
+
+class NjodeSchedule64(C.Structure):
+    """include/njode_f64.h: ``step_dt`` is the float64 clock's own step."""
+    _fields_ = NjodeSchedule._fields_
+
+
+class NjodeBatch64(C.Structure):
+    _fields_ = [('batch_size', C.c_int32), ('n_obs', C.c_int32),
+                ('start_X', C.c_void_p), ('X', C.c_void_p), ('M', C.c_void_p),
+                ('obs_idx', C.c_void_p), ('n_obs_ot', C.c_void_p),
+                ('loss_batch_size', C.c_double)]
 
 
 class NjodeSde(C.Structure):
@@ -286,6 +300,15 @@ def lib():
     L.njode_debug_plan_stamps.argtypes = [vp, C.c_int]
     L.njode_debug_plan_view.argtypes = [C.POINTER(NjodeDims), i32, i32, i32, i32, i32,
                                         C.POINTER(NjodePlanView)]
+    # include/njode_f64.h
+    d64 = (dp, vp, C.POINTER(NjodeBatch64), C.POINTER(NjodeSchedule64), i32, f64)
+    L.njode_f64_supported.argtypes = [dp]
+    L.njode_f64_workspace_bytes.argtypes = [dp, i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.njode_forward_f64.argtypes = [*d64, vp, vp, vp, vp, vp, sz, vp]
+    L.njode_backward_f64.argtypes = [*d64, vp, vp, vp, vp, sz, vp]
+    for name in ('njode_f64_supported', 'njode_f64_workspace_bytes', 'njode_forward_f64',
+                 'njode_backward_f64'):
+        getattr(L, name).restype = C.c_int
     _lib = L
     return L
 

@@ -287,6 +287,12 @@ class NJODE(FlatParams, CallLayer, torch.nn.Module):
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
+    def float64(self):
+        """A float64 twin (``njode_amd.float64.NJODE64``) with this model's parameters widened exactly:
+        forward, gradients and training in double on the GPU.  ``double()`` stays an fp32 evaluation."""
+        from .float64 import twin_of
+        return twin_of(self)
+
     def flat_parameters(self):
         """The flat parameter vector all Linear parameters are views of."""
         self._ensure_flat()
