@@ -148,7 +148,10 @@ def oracle_truth(cfg, sd, b, delta_t, T, dtype, grads=True, masks=None, c_hT=Non
     out, params = oracle_forward(cfg, sdd, cast, delta_t, T, training=True, grads=True, masks=masks, **kw)
     obj = out[1] if c_hT is None else out[1] + (torch.as_tensor(c_hT).to(dtype) * out[0]).sum()
     obj.backward()
-    return out, {k: p.grad.detach().numpy().astype(np.float64) for k, p in params.items()}
+    # (a parameter the objective does not depend on -- the readout of a batch nobody is observed in -- has
+    # no .grad: its gradient is zero)
+    return out, {k: (np.zeros(tuple(p.shape)) if p.grad is None else p.grad.detach().numpy().astype(np.float64))
+                 for k, p in params.items()}
 
 
 def kernel_names(fn):
@@ -187,7 +190,8 @@ def oracle_pair(cfg, sd, b, delta_t, T, predict=False, masks=None, grads=None, *
                                   **kw)
             r = {'hT': out[0].detach().numpy().astype(np.float64), 'g': g}
             if get_loss:
-                r['loss'] = float(out[1].detach())
+                # (a batch without observations: the oracle's loss is the reference's Python 0)
+                r['loss'] = float(out[1].detach()) if torch.is_tensor(out[1]) else float(out[1])
             if predict:
                 r['path_h'] = out[3].detach().numpy().astype(np.float64)
                 r['path_y'] = out[4].detach().numpy().astype(np.float64)

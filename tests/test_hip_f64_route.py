@@ -77,9 +77,12 @@ class Checker:
     def done(self):
         q = self.rows
         worst_key = max(q, key=lambda k: (q[k]['ratio'] or 0.0))
+        # (a truth that is exactly zero -- the gradient behind a dead relu, a loss nobody is observed for --
+        # has the bound 0: an exact result is 0 of it, anything else is beyond it and fails below)
+        over = max((v['err'] / v['bound'] if v['bound'] > 0 else (0.0 if v['err'] == 0 else float('inf')))
+                   for v in q.values())
         _report({'kind': 'ratio', 'case': self.tag, 'worst_ratio': q[worst_key]['ratio'] or 0.0,
-                 'worst_quantity': worst_key, 'worst_err_over_bound': max(v['err'] / v['bound'] for v in q.values()),
-                 'quantities': len(q)})
+                 'worst_quantity': worst_key, 'worst_err_over_bound': over, 'quantities': len(q)})
         assert not self.bad, (self.tag, self.bad)
 
 
