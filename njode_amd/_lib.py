@@ -51,6 +51,9 @@ EXPORTS = ('njode_supported', 'njode_param_count', 'njode_workspace_bytes',
            'njode_online_gen_predict_f32', 'njode_online_gen_run_f32',
            # include/njode_f64.h
            'njode_f64_supported', 'njode_f64_workspace_bytes', 'njode_forward_f64', 'njode_backward_f64',
+           # include/njode_gob.h
+           'njode_gob_supported', 'njode_gob_param_count', 'njode_gob_workspace_bytes',
+           'njode_gob_forward_f32', 'njode_gob_backward_f32',
            # include/njode_selftest.h
            'njode_selftest_dropout_words', 'njode_debug_plan_stamps', 'njode_debug_plan_view')
 ROWS_CLOSEST, ROWS_FIRST_NEAREST = 0, 1     # NJODE_ROWS_* (include/njode_protocol.h)
@@ -101,6 +104,14 @@ class NjodeBatch64(C.Structure):
                 ('start_X', C.c_void_p), ('X', C.c_void_p), ('M', C.c_void_p),
                 ('obs_idx', C.c_void_p), ('n_obs_ot', C.c_void_p),
                 ('loss_batch_size', C.c_double)]
+
+
+GOB_F_BIAS, GOB_F_IMPUTE = 0x1, 0x2      # NJODE_GOB_F_* (include/njode_gob.h)
+
+
+class NjodeGobDims(C.Structure):
+    _fields_ = [('input_size', C.c_int32), ('hidden_size', C.c_int32), ('p_hidden', C.c_int32),
+                ('prep_hidden', C.c_int32), ('cov_hidden', C.c_int32), ('flags', C.c_int32)]
 
 
 class NjodeSde(C.Structure):
@@ -308,6 +319,18 @@ def lib():
     L.njode_backward_f64.argtypes = [*d64, vp, vp, vp, vp, sz, vp]
     for name in ('njode_f64_supported', 'njode_f64_workspace_bytes', 'njode_forward_f64',
                  'njode_backward_f64'):
+        getattr(L, name).restype = C.c_int
+    # include/njode_gob.h
+    gp = C.POINTER(NjodeGobDims)
+    g32 = (gp, vp, C.POINTER(NjodeBatch), C.POINTER(NjodeSchedule), i32, f32, f32, u64)
+    L.njode_gob_supported.argtypes = [gp]
+    L.njode_gob_param_count.argtypes = [gp]
+    L.njode_gob_param_count.restype = sz
+    L.njode_gob_workspace_bytes.argtypes = [gp, i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.njode_gob_forward_f32.argtypes = [*g32, vp, vp, vp, vp, vp, sz, vp]
+    L.njode_gob_backward_f32.argtypes = [*g32, vp, vp, vp, vp, vp, sz, vp]
+    for name in ('njode_gob_supported', 'njode_gob_workspace_bytes', 'njode_gob_forward_f32',
+                 'njode_gob_backward_f32'):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

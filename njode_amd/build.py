@@ -167,8 +167,9 @@ def build(force=False, jobs=None, verbose=True):
                     '-DNJ_MASKED={}'.format(masked), '-DNJ_CURT={}'.format(curt),
                     '-DNJ_RES={}'.format(res), '-DNJ_ACC_TANH={}'.format(masked), '-DNJ_RNN={}'.format(rnn)]
             tasks.append((obj, common + defs + [os.path.join(CSRC, 'njode_cfg.hip')]))
-    # (f64: the float64 route, include/njode_f64.h -- shape-generic, compiled once)
-    for unit in ('api', 'planner', 'prof', 'gen', 'online', 'f64'):
+    # (f64: the float64 route, include/njode_f64.h -- shape-generic, compiled once; gob: the
+    # GRU-ODE-Bayes baseline, include/njode_gob.h -- likewise)
+    for unit in ('api', 'planner', 'prof', 'gen', 'online', 'f64', 'gob'):
         tasks.append((os.path.join(OBJ, unit + '.o'), common + [os.path.join(CSRC, 'njode_{}.hip'.format(unit))]))
     # the batch producer spells out the reference's float64 expression trees: no contraction
     cmd = common + ['-ffp-contract=off', os.path.join(CSRC, 'njode_producer.hip')]
@@ -208,7 +209,7 @@ def build(force=False, jobs=None, verbose=True):
     if parts_only:                                                 # that only touches those parts
         keep = tuple('_{}.o'.format(x) for x in parts_only.split(',')) + (
             'api.o', 'planner.o', 'prof.o', 'producer.o', 'condexp.o', 'protocol.o', 'records.o', 'gen.o',
-            'online.o', 'f64.o')
+            'online.o', 'f64.o', 'gob.o')
         for t in todo:
             if not t[0].endswith(keep) and os.path.exists(t[0]):
                 restamp(t)

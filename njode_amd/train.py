@@ -30,7 +30,7 @@ import time
 import numpy as np
 import torch
 
-from . import data_utils, device_data, parallel, stock_model
+from . import data_utils, device_data, gob_train, parallel, stock_model
 from .run import Run, new_model_and_optimizer, plan_ahead_on, wants_prefetch
 
 METR_COLUMNS = ['epoch', 'train_time', 'eval_time', 'train_loss', 'eval_loss',
@@ -83,7 +83,22 @@ def train(dataset_arrays, metadata, epochs=1, batch_size=100, learning_rate=1e-3
     dropout stream.  ``device_eval=True``: ``optimal_eval_loss`` and (``evaluate=True``)
     ``evaluation_mean_diff`` come from the analytic conditional expectation on the GPU
     (``device_data.cond_exp``, ``NJODE.evaluate_device``) on the validation batch's device copies
-    instead of the host's numpy walk; an epoch's metrics then reach the host in one read."""
+    instead of the host's numpy walk; an epoch's metrics then reach the host in one read.
+
+    ``other_model='GRU_ODE_Bayes'`` (with the reference's ``'GRU_ODE_Bayes-mixing'``, ``-impute``,
+    ``-p_hidden``, ``-prep_hidden``, ``-cov_hidden``, ``-logvar``, ``-full_gru_ode``, ``-solver``
+    options and defaults) trains the baseline of ``gru_ode_bayes`` instead: plain autograd steps
+    with ``torch.optim.Adam``; any other value, a process group of more than one rank and
+    ``device_eval=True`` raise ``ValueError``."""
+    if 'other_model' in options:
+        # the reference's baseline (train.py:354-392): njode_amd/gob_train.py.  fused, plan_ahead and
+        # device_collate belong to NJ-ODE and do not apply
+        gob_train.check_other_model(options['other_model'], device_eval)
+        return gob_train.train_baseline(
+            dataset_arrays, metadata, options, METR_COLUMNS + (['evaluation_mean_diff'] if evaluate else []),
+            epochs, batch_size, learning_rate, hidden_size, bias, dropout_rate, test_size, seed, device,
+            evaluate, shuffle_seed, log, max_steps_per_epoch, model_path, model_id, save_every,
+            resume_training, load_best, init_state)
     stock_paths, observed_dates, nb_obs = dataset_arrays
     delta_t, T = metadata['dt'], metadata['maturity']
     input_size = output_size = metadata['dimension']
