@@ -1,8 +1,93 @@
 """
-Flat parameter storage of ``models.NJODE``: every parameter is a view of one fp32 vector laid out
-as the C ABI expects, so the kernels read one pointer and the gradient comes back as one vector.
+Flat parameter storage: every parameter of a model is a view of one vector laid out as the C ABI
+expects, so the kernels read one pointer and the gradient comes back as one vector.
+``lay_out_flat`` makes the vector; ``FlatVector`` is the storage of the float64 route and of
+GRU-ODE-Bayes, ``FlatParams`` that of ``models.NJODE`` (fp32, with the hot loop's fast path).
 """
+import copy
+
 import torch
+
+
+def lay_out_flat(slots, dtype):
+    """``slots`` = [(parameter or None, slot size, shape)] in the C ABI's order -> (flat, slices,
+    params, present): one ``dtype`` vector holding the parameters' values, which become views of it;
+    ``(offset, size, shape)`` and the parameter of every slot that has one; ``present``: a mask with
+    zeros over the slots that have none (``None`` when every slot has one)."""
+    dev = slots[0][0].device
+    total = sum(n for _, n, _ in slots)
+    flat = torch.zeros(total, dtype=dtype, device=dev)
+    slices, params, off, present = [], [], 0, None
+    for p, n, shape in slots:
+        if p is not None:
+            flat[off:off + n].copy_(p.data.reshape(-1).to(dtype))
+            p.data = flat[off:off + n].view(shape)
+            slices.append((off, n, shape))
+            params.append(p)
+        else:
+            # a slot without a parameter (bias=False, models.py:140-166): the kernels read it
+            # as zeros and WRITE its gradient; it is not a parameter, so the fused optimizer
+            # must leave it alone (FusedAdam.step multiplies the gradient by this mask)
+            if present is None:
+                present = torch.ones(total, dtype=dtype, device=dev)
+            present[off:off + n] = 0.0
+        off += n
+    return flat, slices, params, present
+
+
+class FlatVector:
+    """Base of a ``torch.nn.Module`` (named before it) whose kernel parameters are ``_flat_dtype``
+    views of one flat vector: ``_flat``, ``_flat_params``, ``_param_slices``.  The model says which
+    parameters, in ``_flat_slots()``, and sets the three attributes to ``None`` before it creates
+    its parameters."""
+    _flat_dtype = torch.float32
+
+    def _views_in_place(self, which=None):
+        """Whether the parameters (``which``: indices, default all) still are views of the flat vector."""
+        if self._flat is None:
+            return False
+        base, size = self._flat.data_ptr(), self._flat.element_size()
+        for i in range(len(self._flat_params)) if which is None else which:
+            p = self._flat_params[i]
+            if p.data_ptr() != base + size * self._param_slices[i][0] or p.dtype != self._flat_dtype:
+                return False
+        return True
+
+    def _ensure_flat(self):
+        """Every kernel parameter a view of one flat vector (values are kept; a parameter of another
+        dtype is converted).  Re-done after ``.to()`` / ``.cuda()`` moved the parameters."""
+        if not self._views_in_place():
+            self._flat, self._param_slices, self._flat_params, _ = lay_out_flat(self._flat_slots(),
+                                                                                self._flat_dtype)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if getattr(self, '_flat', None) is not None:
+            self._ensure_flat()
+        return out
+
+    def _split_flat(self, flat):
+        """A flat vector (gradient) as views shaped like the parameters, in ``_flat_params`` order."""
+        return [flat[off:off + n].view(shape) for (off, n, shape) in self._param_slices]
+
+    def flat_parameters(self):
+        """The flat vector the kernels' parameters are views of."""
+        self._ensure_flat()
+        return self._flat
+
+    def _fresh_runtime_state(self):
+        """Hook: set what a new model and a copy of one start without (``_ring`` and ``_schedules``
+        are ``None`` in a copy when this is called)."""
+
+    def __deepcopy__(self, memo):
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        skip = ('_flat', '_param_slices', '_flat_params', '_ring', '_schedules')
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = None if k in skip else copy.deepcopy(v, memo)
+        new._fresh_runtime_state()
+        new._ensure_flat()
+        return new
 
 
 class FlatParams:
@@ -56,29 +141,8 @@ class FlatParams:
                     return
             if self._views_in_place(range(len(self._flat_params))):
                 return
-        slots = self._flat_slots()
-        dev = slots[0][0].device
-        total = sum(n for _, n, _ in slots)
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        slices, params, off, present = [], [], 0, None
-        for p, n, shape in slots:
-            if p is not None:
-                flat[off:off + n].copy_(p.data.reshape(-1).to(torch.float32))
-                p.data = flat[off:off + n].view(shape)
-                slices.append((off, n, shape))
-                params.append(p)
-            else:
-                # a slot without a parameter (bias=False, models.py:140-166): the kernels read it
-                # as zeros and WRITE its gradient; it is not a parameter, so the fused optimizer
-                # must leave it alone (FusedAdam.step multiplies the gradient by this mask)
-                if present is None:
-                    present = torch.ones(total, dtype=torch.float32, device=dev)
-                present[off:off + n] = 0.0
-            off += n
-        self._flat, self._param_slices, self._flat_params = flat, slices, params
-        self._flat_present = present
+        self._flat, self._param_slices, self._flat_params, self._flat_present = lay_out_flat(
+            self._flat_slots(), torch.float32)
         self._flat_grad = self._grad_bucket = None
 
-    def _split_flat(self, flat):
-        """A flat vector (gradient) as views shaped like the parameters, in ``_flat_params`` order."""
-        return [flat[off:off + n].view(shape) for (off, n, shape) in self._param_slices]
+    _split_flat = FlatVector._split_flat

@@ -13,7 +13,7 @@
 
 #include "../../include/njode_f64.h"
 #include "njode_gen_host.h"
-#include "njode_hostlib.h"
+#include "njode_pathwalk.h"
 
 using namespace njode;
 
@@ -491,60 +491,11 @@ __global__ void k_f64_bwd(const FArgs A) {
   }
 }
 
-// Wt[i][j] = W[j][i] of every layer, at the layer's own offset (bias slots are not used)
-__global__ void k_f64_transpose(const FModel m, const double* __restrict__ params, double* __restrict__ wt) {
-  const FNet* nets[3] = {&m.ode, &m.enc, &m.dec};
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < m.P; e += gridDim.x * blockDim.x) {
-    for (int n = 0; n < 3; ++n)
-      for (int l = 0; l < nets[n]->nl; ++l) {
-        const FLayer& L = nets[n]->l[l];
-        const int q = e - L.w_off;
-        if (q >= 0 && q < L.n_in * L.n_out) {
-          const int j = q / L.n_in, i = q - j * L.n_in;
-          wt[L.w_off + (size_t)i * L.n_out + j] = params[e];
-        }
-      }
-  }
-}
-
-__global__ void k_f64_rows_clear(int* row_of, size_t n) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x)
-    row_of[e] = -1;
-}
-__global__ void k_f64_rows(const int* __restrict__ obs_idx, const int* __restrict__ time_ptr, int n_obs,
-                           int nt, int B, int* row_of) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_obs || nt <= 0) return;
-  const int p = obs_idx[r];
-  if (p < 0 || p >= B) return;
-  int lo = 0, hi = nt - 1;   // the last slice whose first row is <= r
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (time_ptr[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  row_of[(size_t)lo * B + p] = r;
-}
-
 // loss = (sum of the paths' terms, in a fixed tree) / loss_batch_size
 __global__ void k_f64_loss(const double* __restrict__ part, int B, double lbs, double* loss) {
-  __shared__ double red[256];
-  double acc = 0.0;
-  for (int p = threadIdx.x; p < B; p += 256) acc += part[p];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = red[0] / lbs;
-}
-
-__global__ void k_f64_reduce(const double* __restrict__ slabs, int S, int P, double* __restrict__ grad) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= P) return;
-  double acc = 0.0;
-  for (int sidx = 0; sidx < S; ++sidx) acc += slabs[(size_t)sidx * P + e];
-  grad[e] = acc;
+  double sum[1];
+  tree_sum_256<1>(part, B, 0, sum);
+  if (threadIdx.x == 0) loss[0] = sum[0] / lbs;
 }
 
 // ---- host ----------------------------------------------------------------------------------------
@@ -658,11 +609,12 @@ bool supported(const NjodeDims* dims, FModel& m) {
   return gen::gen_supported(dims);   // (leaves its own reason)
 }
 
-int slab_count(const FModel& m, int B) {
-  size_t s = SLAB_BUDGET / ((size_t)m.P * 8);
-  if (s > (size_t)MAX_SLABS) s = MAX_SLABS;
-  if (s > (size_t)B) s = B;
-  return s < 1 ? 1 : (int)s;
+// every layer's matrix: the forward reads them transposed (bias slots are not used)
+MatTable weight_matrices(const FModel& m) {
+  MatTable t = {};
+  for (const FNet* N : {&m.ode, &m.enc, &m.dec})
+    for (int l = 0; l < N->nl; ++l) t.add(N->l[l].w_off, N->l[l].n_out, N->l[l].n_in);
+  return t;
 }
 
 struct Layout : Arena {
@@ -673,7 +625,7 @@ struct Layout : Arena {
 
 Layout make_layout(const FModel& m, int B, int n_obs, int nt, int K, int flags) {
   Layout L;
-  const size_t b = B, no = n_obs > 0 ? n_obs : 1, k = K > 0 ? K : 1, t = nt > 0 ? nt : 1;
+  const size_t b = B, no = at_least_1(n_obs), k = at_least_1(K), t = at_least_1(nt);
   L.step_dt = L.take(k * 8);
   L.step_t = L.take(k * 4);
   L.k_jump = L.take(t * 4);
@@ -682,7 +634,7 @@ Layout make_layout(const FModel& m, int B, int n_obs, int nt, int K, int flags) 
   L.wt = L.take((size_t)m.P * 8);
   L.row_of = L.take(t * b * 4);
   L.loss_part = L.take(b * 8);
-  L.S = slab_count(m, B);
+  L.S = slab_count((size_t)m.P * 8, SLAB_BUDGET, MAX_SLABS, B);
   if (flags & NJODE_C_SAVE_BWD) {
     L.h_step = L.take(k * b * m.H * 8);
     L.h_bj = L.take(no * m.H * 8);
@@ -696,15 +648,13 @@ Layout make_layout(const FModel& m, int B, int n_obs, int nt, int K, int flags) 
 }
 
 constexpr int KNOWN_FLAGS = NJODE_C_GET_LOSS | NJODE_C_RETURN_PATH | NJODE_C_SAVE_BWD;
+constexpr const char* BAD_FLAG = "call flag the float64 route does not take";
 
 // every refusal a call makes before it launches anything (array contents: the host schedule only)
 int check_call(const FModel& m, const NjodeBatch64* b, const NjodeSchedule64* s, int flags, const double* params,
                const void* ws, bool forward) {
-  if (!b || !s) return fail(NJODE_E_BADARG, "null argument");
-  if (flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "call flag the float64 route does not take");
-  const int n_obs = b->n_obs, K = s->n_steps, nt = s->n_times;
-  if (b->batch_size <= 0 || n_obs < 0 || K < 0 || nt < 0) return fail(NJODE_E_BADARG, "negative size");
-  if (!params) return fail(NJODE_E_BADARG, "null params");
+  if (int rc = check_sizes_and_params(b, s, flags, KNOWN_FLAGS, BAD_FLAG, params)) return rc;
+  const int n_obs = b->n_obs, nt = s->n_times;
   if (!b->start_X || (n_obs > 0 && (!b->X || !b->obs_idx))) return fail(NJODE_E_BADARG, "null batch array");
   if (m.masked && n_obs > 0 && !b->M) return fail(NJODE_E_BADARG, "masked model needs M");
   if (flags & NJODE_C_GET_LOSS) {
@@ -713,24 +663,8 @@ int check_call(const FModel& m, const NjodeBatch64* b, const NjodeSchedule64* s,
     if (!(b->loss_batch_size > 0.0)) return fail(NJODE_E_BADARG, "loss_batch_size must be positive");
   }
   if (n_obs > 0 && nt == 0) return fail(NJODE_E_BADARG, "observation rows without observation times");
-  if (!ws || ((uintptr_t)ws & 255)) return fail(NJODE_E_BADARG, "workspace null or not aligned to 256 bytes");
-  if (forward) {
-    if ((K > 0 && (!s->step_dt || !s->step_t)) || (nt > 0 && (!s->k_jump || !s->time_f32)) || !s->time_ptr)
-      return fail(NJODE_E_BADARG, "null schedule array");
-    if (s->time_ptr[0] != 0 || s->time_ptr[nt] != n_obs) return fail(NJODE_E_BADARG, "time_ptr does not span the rows");
-    int kprev = 0;
-    for (int i = 0; i < nt; ++i) {
-      if (s->time_ptr[i + 1] < s->time_ptr[i]) return fail(NJODE_E_BADARG, "time_ptr decreases");
-      if (s->k_jump[i] < kprev || s->k_jump[i] > K) return fail(NJODE_E_BADARG, "k_jump out of order or range");
-      kprev = s->k_jump[i];
-    }
-  }
-  return NJODE_OK;
-}
-
-int set_lds(const void* fn, int bytes) {
-  if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return NJODE_OK;
+  if (int rc = check_workspace_ptr(ws)) return rc;
+  return forward ? check_schedule_walk(s, n_obs) : NJODE_OK;
 }
 
 void fill_args(FArgs& A, const FModel& m, const Layout& L, char* ws, const NjodeBatch64* b,
@@ -774,7 +708,7 @@ extern "C" int njode_f64_workspace_bytes(const NjodeDims* dims, int32_t B, int32
   FModel m;
   if (!supported(dims, m)) return NJODE_E_UNSUPPORTED;
   if (!out || B <= 0 || n_obs < 0 || nt < 0 || K < 0) return fail(NJODE_E_BADARG, "bad size");
-  if (call_flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "call flag the float64 route does not take");
+  if (call_flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "%s", BAD_FLAG);
   *out = make_layout(m, B, n_obs, nt, K, call_flags).total;
   return NJODE_OK;
 }
@@ -791,7 +725,7 @@ extern "C" int njode_forward_f64(const NjodeDims* dims, const double* params, co
   if ((flags & NJODE_C_RETURN_PATH) && (!path_h || !path_y)) return fail(NJODE_E_BADARG, "null output");
   const int B = b->batch_size, n_obs = b->n_obs, nt = s->n_times, K = s->n_steps;
   const Layout L = make_layout(m, B, n_obs, nt, K, flags);
-  if (ws_bytes < L.total) return fail(NJODE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, L.total);
+  if ((rc = check_workspace_size(ws_bytes, L.total))) return rc;
   char* ws = (char*)workspace;
   const int lds = lds_doubles(m, false) * 8;
   if ((rc = set_lds((const void*)k_f64_fwd, lds))) return rc;
@@ -811,16 +745,8 @@ extern "C" int njode_forward_f64(const NjodeDims* dims, const double* params, co
   A.hT = hT;
   A.path_h = path_h;
   A.path_y = path_y;
-  {
-    ProfScope ps("k_f64_transpose", st);
-    k_f64_transpose<<<cdiv(m.P, 256) > 1024 ? 1024 : cdiv(m.P, 256), 256, 0, st>>>(m, params, (double*)(ws + L.wt));
-  }
-  if (nt > 0) {
-    ProfScope ps("k_f64_rows", st);
-    const size_t n = (size_t)nt * B;
-    k_f64_rows_clear<<<cdiv(n, 256) > 2048 ? 2048 : cdiv(n, 256), 256, 0, st>>>(A.row_of, n);
-    if (n_obs > 0) k_f64_rows<<<cdiv(n_obs, 256), 256, 0, st>>>(b->obs_idx, A.time_ptr, n_obs, nt, B, A.row_of);
-  }
+  transpose_weights(weight_matrices(m), m.P, params, (double*)(ws + L.wt), "k_f64_transpose", st);
+  build_row_table(A.row_of, b->obs_idx, A.time_ptr, n_obs, nt, B, "k_f64_rows", st);
   {
     ProfScope ps("k_f64_fwd", st);
     k_f64_fwd<<<B, m.nth, lds, st>>>(A);
@@ -847,7 +773,7 @@ extern "C" int njode_backward_f64(const NjodeDims* dims, const double* params, c
   if ((flags & NJODE_C_GET_LOSS) && !grad_loss) return fail(NJODE_E_BADARG, "null grad_loss");
   const int B = b->batch_size, n_obs = b->n_obs, nt = s->n_times, K = s->n_steps;
   const Layout L = make_layout(m, B, n_obs, nt, K, flags);
-  if (ws_bytes < L.total) return fail(NJODE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, L.total);
+  if ((rc = check_workspace_size(ws_bytes, L.total))) return rc;
   char* ws = (char*)workspace;
   const int lds = lds_doubles(m, true) * 8;
   if ((rc = set_lds((const void*)k_f64_bwd, lds))) return rc;
@@ -860,10 +786,7 @@ extern "C" int njode_backward_f64(const NjodeDims* dims, const double* params, c
     ProfScope ps("k_f64_bwd", st);
     k_f64_bwd<<<L.S, m.nth, lds, st>>>(A);
   }
-  {
-    ProfScope ps("k_f64_reduce", st);
-    k_f64_reduce<<<cdiv(m.P, 256), 256, 0, st>>>(A.slabs, L.S, m.P, grad_params);
-  }
+  reduce_slabs(A.slabs, L.S, m.P, grad_params, "k_f64_reduce", st);
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
 }

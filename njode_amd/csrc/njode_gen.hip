@@ -496,12 +496,6 @@ int prepare(Call& c, const NjodeDims* dims, const float* params, const NjodeBatc
   return NJODE_OK;
 }
 
-int set_lds(const void* fn, int bytes) {
-  if (bytes > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return NJODE_OK;
-}
-
 }  // namespace
 
 namespace njode {

@@ -28,7 +28,7 @@
 
 #include "../../include/njode_gob.h"
 #include "njode_call.h"
-#include "njode_hostlib.h"
+#include "njode_pathwalk.h"
 
 using namespace njode;
 
@@ -682,60 +682,14 @@ __global__ void __launch_bounds__(64) k_gob_bwd(const GArgs A) {
   }
 }
 
-// WT[i][j] = W[j][i] of the matrices the forward reads transposed, at their own offsets
-__global__ void k_gob_transpose(const GModel m, const float* __restrict__ params, float* __restrict__ wt) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < m.P; e += gridDim.x * blockDim.x)
-    for (int t = 0; t < NMAT; ++t) {
-      const int q = e - m.t_off[t];
-      if (m.t_out[t] > 0 && q >= 0 && q < m.t_in[t] * m.t_out[t]) {
-        const int j = q / m.t_in[t], i = q - j * m.t_in[t];
-        wt[m.t_off[t] + (size_t)i * m.t_out[t] + j] = params[e];
-      }
-    }
-}
-
-__global__ void k_gob_rows_clear(int* row_of, size_t n) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x)
-    row_of[e] = -1;
-}
-__global__ void k_gob_rows(const int* __restrict__ obs_idx, const int* __restrict__ time_ptr, int n_obs,
-                           int nt, int B, int* row_of) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_obs || nt <= 0) return;
-  const int p = obs_idx[r];
-  if (p < 0 || p >= B) return;
-  int lo = 0, hi = nt - 1;   // the last slice whose first row is <= r
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (time_ptr[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  row_of[(size_t)lo * B + p] = r;
-}
-
 // loss = {loss_1 + mixing loss_2, loss_1}: the paths' terms in a fixed tree
 __global__ void k_gob_loss(const double* __restrict__ part, int B, float mixing, float* loss) {
-  __shared__ double r1[256], r2[256];
-  double a1 = 0.0, a2 = 0.0;
-  for (int p = threadIdx.x; p < B; p += 256) { a1 += part[p]; a2 += part[B + p]; }
-  r1[threadIdx.x] = a1;
-  r2[threadIdx.x] = a2;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { r1[threadIdx.x] += r1[threadIdx.x + w]; r2[threadIdx.x] += r2[threadIdx.x + w]; }
-    __syncthreads();
-  }
+  double sum[2];
+  tree_sum_256<2>(part, B, B, sum);
   if (threadIdx.x == 0) {
-    loss[0] = (float)(r1[0] + (double)mixing * r2[0]);
-    loss[1] = (float)r1[0];
+    loss[0] = (float)(sum[0] + (double)mixing * sum[1]);
+    loss[1] = (float)sum[0];
   }
-}
-
-__global__ void k_gob_reduce(const float* __restrict__ slabs, int S, int P, float* __restrict__ grad) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= P) return;
-  double acc = 0.0;
-  for (int s = 0; s < S; ++s) acc += (double)slabs[(size_t)s * P + e];
-  grad[e] = (float)acc;
 }
 
 // ---- host ----------------------------------------------------------------------------------------
@@ -784,11 +738,12 @@ bool build_model(const NjodeGobDims* d, GModel& m) {
   return true;
 }
 
-int slab_count(const GModel& m, int B) {
-  size_t s = SLAB_BUDGET / ((size_t)m.P * 4);
-  if (s > (size_t)MAX_SLABS) s = MAX_SLABS;
-  if (s > (size_t)B) s = B;
-  return s < 1 ? 1 : (int)s;
+// the matrices the forward reads transposed (GModel keeps its own lists: it is a kernel argument
+// of the walk and the sweep, whose layout stays as it is)
+MatTable transposed_matrices(const GModel& m) {
+  MatTable t = {};
+  for (int i = 0; i < NMAT; ++i) t.add(m.t_off[i], m.t_out[i], m.t_in[i]);
+  return t;
 }
 
 struct Layout : Arena {
@@ -798,12 +753,12 @@ struct Layout : Arena {
 
 Layout make_layout(const GModel& m, int B, int n_obs, int nt, int K, int flags) {
   Layout L;
-  const size_t b = B, no = n_obs > 0 ? n_obs : 1, k = K > 0 ? K : 1, t = nt > 0 ? nt : 1;
+  const size_t b = B, no = at_least_1(n_obs), k = at_least_1(K), t = at_least_1(nt);
   L.sched = L.take(((size_t)2 * K + 3 * (size_t)nt + 1) * 4);
   L.wt = L.take((size_t)m.P * 4);
   L.row_of = L.take(t * b * 4);
   L.loss_part = L.take(2 * b * 8);
-  L.S = slab_count(m, B);
+  L.S = slab_count((size_t)m.P * 4, SLAB_BUDGET, MAX_SLABS, B);
   L.h_step = L.h_bj = L.h_end = L.slabs = 0;
   if (flags & NJODE_C_SAVE_BWD) {
     L.h_step = L.take(k * b * m.H * 4);
@@ -815,36 +770,18 @@ Layout make_layout(const GModel& m, int B, int n_obs, int nt, int K, int flags) 
 }
 
 constexpr int KNOWN_FLAGS = NJODE_C_TRAIN | NJODE_C_RETURN_PATH | NJODE_C_SAVE_BWD;
+constexpr const char* BAD_FLAG = "call flag the GRU-ODE-Bayes calls do not take";
 
 // every refusal a call makes before it launches anything (array contents: the host schedule only)
 int check_gob(const NjodeBatch* b, const NjodeSchedule* s, int flags, const float* params, const void* ws,
               float dropout_p, bool forward) {
-  if (!b || !s) return fail(NJODE_E_BADARG, "null argument");
-  if (flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "call flag the GRU-ODE-Bayes calls do not take");
-  const int n_obs = b->n_obs, K = s->n_steps, nt = s->n_times;
-  if (b->batch_size <= 0 || n_obs < 0 || K < 0 || nt < 0) return fail(NJODE_E_BADARG, "negative size");
-  if (!params) return fail(NJODE_E_BADARG, "null params");
+  if (int rc = check_sizes_and_params(b, s, flags, KNOWN_FLAGS, BAD_FLAG, params)) return rc;
+  const int n_obs = b->n_obs, nt = s->n_times;
   if (!b->start_X || (n_obs > 0 && (!b->X || !b->obs_idx || !b->M))) return fail(NJODE_E_BADARG, "null batch array");
   if (n_obs > 0 && nt == 0) return fail(NJODE_E_BADARG, "observation rows without observation times");
   if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(NJODE_E_BADARG, "dropout_p");
-  if (!ws || ((uintptr_t)ws & 255)) return fail(NJODE_E_BADARG, "workspace null or not aligned to 256 bytes");
-  if (forward) {
-    if ((K > 0 && (!s->step_dt || !s->step_t)) || (nt > 0 && (!s->k_jump || !s->time_f32)) || !s->time_ptr)
-      return fail(NJODE_E_BADARG, "null schedule array");
-    if (s->time_ptr[0] != 0 || s->time_ptr[nt] != n_obs) return fail(NJODE_E_BADARG, "time_ptr does not span the rows");
-    int kprev = 0;
-    for (int i = 0; i < nt; ++i) {
-      if (s->time_ptr[i + 1] < s->time_ptr[i]) return fail(NJODE_E_BADARG, "time_ptr decreases");
-      if (s->k_jump[i] < kprev || s->k_jump[i] > K) return fail(NJODE_E_BADARG, "k_jump out of order or range");
-      kprev = s->k_jump[i];
-    }
-  }
-  return NJODE_OK;
-}
-
-int set_lds(const void* fn, int bytes) {
-  if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return NJODE_OK;
+  if (int rc = check_workspace_ptr(ws)) return rc;
+  return forward ? check_schedule_walk(s, n_obs) : NJODE_OK;
 }
 
 void fill_args(GArgs& A, const GModel& m, const Layout& L, char* ws, const NjodeBatch* b, const NjodeSchedule* s,
@@ -890,7 +827,7 @@ extern "C" int njode_gob_workspace_bytes(const NjodeGobDims* dims, int32_t B, in
   GModel m;
   if (!build_model(dims, m)) return NJODE_E_UNSUPPORTED;
   if (!out || B <= 0 || n_obs < 0 || nt < 0 || K < 0) return fail(NJODE_E_BADARG, "bad size");
-  if (call_flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "call flag the GRU-ODE-Bayes calls do not take");
+  if (call_flags & ~KNOWN_FLAGS) return fail(NJODE_E_BADARG, "%s", BAD_FLAG);
   *out = make_layout(m, B, n_obs, nt, K, call_flags).total;
   return NJODE_OK;
 }
@@ -907,7 +844,7 @@ extern "C" int njode_gob_forward_f32(const NjodeGobDims* dims, const float* para
   if ((flags & NJODE_C_RETURN_PATH) && (!path_h || !path_p)) return fail(NJODE_E_BADARG, "null output");
   const int B = b->batch_size, n_obs = b->n_obs, nt = s->n_times, K = s->n_steps;
   const Layout L = make_layout(m, B, n_obs, nt, K, flags);
-  if (ws_bytes < L.total) return fail(NJODE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, L.total);
+  if ((rc = check_workspace_size(ws_bytes, L.total))) return rc;
   char* ws = (char*)workspace;
   const int lds = 3 * m.H * m.HS * 4;
   if ((rc = set_lds((const void*)k_gob_fwd, lds))) return rc;
@@ -918,16 +855,8 @@ extern "C" int njode_gob_forward_f32(const NjodeGobDims* dims, const float* para
   A.hT = hT;
   A.path_h = path_h;
   A.path_p = path_p;
-  {
-    ProfScope ps("k_gob_transpose", st);
-    k_gob_transpose<<<cdiv(m.P, 256) > 1024 ? 1024 : cdiv(m.P, 256), 256, 0, st>>>(m, params, (float*)(ws + L.wt));
-  }
-  if (nt > 0) {
-    ProfScope ps("k_gob_rows", st);
-    const size_t n = (size_t)nt * B;
-    k_gob_rows_clear<<<cdiv(n, 256) > 2048 ? 2048 : cdiv(n, 256), 256, 0, st>>>(A.row_of, n);
-    if (n_obs > 0) k_gob_rows<<<cdiv(n_obs, 256), 256, 0, st>>>(b->obs_idx, A.time_ptr, n_obs, nt, B, A.row_of);
-  }
+  transpose_weights(transposed_matrices(m), m.P, params, (float*)(ws + L.wt), "k_gob_transpose", st);
+  build_row_table(A.row_of, b->obs_idx, A.time_ptr, n_obs, nt, B, "k_gob_rows", st);
   {
     ProfScope ps("k_gob_fwd", st);
     k_gob_fwd<<<B, 64, lds, st>>>(A);
@@ -953,7 +882,7 @@ extern "C" int njode_gob_backward_f32(const NjodeGobDims* dims, const float* par
   if (!grad_params || !grad_loss || !grad_loss_1) return fail(NJODE_E_BADARG, "null gradient argument");
   const int B = b->batch_size, n_obs = b->n_obs, nt = s->n_times, K = s->n_steps;
   const Layout L = make_layout(m, B, n_obs, nt, K, flags);
-  if (ws_bytes < L.total) return fail(NJODE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, L.total);
+  if ((rc = check_workspace_size(ws_bytes, L.total))) return rc;
   char* ws = (char*)workspace;
   const int lds = (3 * m.H * m.HS + 3 * m.H * m.H) * 4;
   if ((rc = set_lds((const void*)k_gob_bwd, lds))) return rc;
@@ -967,10 +896,7 @@ extern "C" int njode_gob_backward_f32(const NjodeGobDims* dims, const float* par
     ProfScope ps("k_gob_bwd", st);
     k_gob_bwd<<<L.S, 64, lds, st>>>(A);
   }
-  {
-    ProfScope ps("k_gob_reduce", st);
-    k_gob_reduce<<<cdiv(m.P, 256), 256, 0, st>>>(A.slabs, L.S, m.P, grad_params);
-  }
+  reduce_slabs(A.slabs, L.S, m.P, grad_params, "k_gob_reduce", st);
   HIP_TRY(hipGetLastError());
   return NJODE_OK;
 }

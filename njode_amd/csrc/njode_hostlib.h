@@ -28,6 +28,13 @@ inline int fail(int code, const char* fmt, ...) {
       return ::njode::fail(NJODE_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
   } while (0)
 
+// a kernel that asks for more dynamic LDS than the 48 KB a launch gets without saying so (static:
+// every unit has its own, the library exports none)
+static inline int set_lds(const void* fn, int bytes) {
+  if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  return NJODE_OK;
+}
+
 // ---- optional per-kernel timing (njode_profile_enable / njode_profile_read, njode_prof.hip):
 // HIP events recorded on the launch stream around each kernel
 void prof_mark(const char* name, hipStream_t st, bool begin);

@@ -13,14 +13,15 @@ Same constructor arguments, ``state_dict`` keys, ``forward`` signature and retur
 ABI's order (bias slots always present), so plain ``torch.optim`` on ``parameters()`` trains in
 double with nothing else.  Not built: the GRU jump (``use_rnn``) and dropout in train mode.
 """
-import collections
 import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, models
-from .schedule import PinnedRing, _walk_clock
+from ._flat import FlatVector
+from ._slabcall import _SlabCall, _SlabFunction, issuing
+from .schedule import ScheduleCache, _walk_clock
 
 
 class Schedule64:
@@ -55,49 +56,13 @@ class Schedule64:
         w[K:K + nt] = self.k_jump
         w[K + nt:K + 2 * nt].view(np.float32)[:] = self.time_f32
         w[K + 2 * nt:K + 3 * nt + 1] = time_ptr
-        base = buf.ctypes.data
+        return self.struct(buf.ctypes.data)
+
+    def struct(self, base):
+        """The ``NjodeSchedule64`` over a buffer ``pack_into`` has filled, at address ``base``."""
+        K, nt = self.n_steps, self.n_times
         return _lib.NjodeSchedule64(K, nt, base, base + 8 * K, base + 12 * K, base + 12 * K + 4 * nt,
                                     base + 12 * K + 8 * nt)
-
-
-class _Call64:
-    """One forward call: structs, flags, the buffers they point into and the workspace, kept alive
-    for the backward."""
-    __slots__ = ('dims', 'batch', 'sched', 'flags', 'weight', 'ws', 'keep', 'sizes', 'flat', 'has_loss')
-
-
-class _NJODE64Function(torch.autograd.Function):
-    """outs = F(params): (loss, hT), or (hT,) of a ``get_loss=False`` call; backward = the exact
-    discrete adjoint (``njode_backward_f64``), which takes the upstream gradient of hT as well."""
-
-    @staticmethod
-    def forward(ctx, model, call, outs, *params):
-        ctx.model, ctx.call = model, call
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(*params)
-        return outs
-
-    @staticmethod
-    def backward(ctx, *grads):
-        model, call = ctx.model, ctx.call
-        ctx.saved_tensors       # (autograd's own check: the parameters are the forward's)
-        if call.flat is not model._flat:
-            raise RuntimeError('the parameters of this NJODE64 forward were moved before its backward')
-        grad_loss, grad_hT = grads if call.has_loss else (None, grads[0])
-        dev = call.flat.device
-        B, H = call.sizes[0], model.hidden_size
-        gl = gh = None
-        if call.has_loss:
-            gl = (torch.zeros(1, dtype=torch.float64, device=dev) if grad_loss is None
-                  else grad_loss.to(device=dev, dtype=torch.float64).reshape(1).contiguous())
-        if grad_hT is not None:
-            gh = grad_hT.to(device=dev, dtype=torch.float64).reshape(B, H).contiguous()
-        grad_flat = torch.empty_like(call.flat)
-        _lib.check(_lib.lib().njode_backward_f64(
-            ctypes.byref(call.dims), call.flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
-            call.flags, call.weight, _lib.ptr_arg(gl), _lib.ptr_arg(gh), grad_flat.data_ptr(),
-            call.ws.data_ptr(), call.ws.numel(), _lib.stream_arg(dev)))
-        return (None, None, None) + tuple(model._split_flat(grad_flat))
 
 
 def _nn_desc(desc):
@@ -108,8 +73,12 @@ def _nn_desc(desc):
     return tuple((w, 'tanh' if a == _lib.ACT_TANH else 'relu') for w, a in zip(widths, acts))
 
 
-class NJODE64(torch.nn.Module):
-    """NJ-ODE in float64 on the GPU; the interface of ``models.NJODE``."""
+class NJODE64(FlatVector, torch.nn.Module):
+    """NJ-ODE in float64 on the GPU; the interface of ``models.NJODE``.  The autograd node of a
+    saved forward (``_SlabFunction``) has the outputs (loss, hT), or (hT,) of a ``get_loss=False``
+    call; its backward takes the upstream gradient of hT as well."""
+    _flat_dtype = torch.float64
+    _moved_error = 'the parameters of this NJODE64 forward were moved before its backward'
 
     def __init__(self, input_size, hidden_size, output_size, ode_nn, readout_nn, enc_nn,
                  use_rnn, bias=True, dropout_rate=0, solver="euler", weight=0.5,
@@ -132,8 +101,8 @@ class NJODE64(torch.nn.Module):
         self.bias = bias
         self._descs = (models._desc_of(ode_nn), models._desc_of(enc_nn), models._desc_of(readout_nn))
         self._flat = self._param_slices = self._flat_params = self._dims = self._ring = None
-        self._schedules = collections.OrderedDict()
-        self._get_dims()        # (refuses what the library has no float64 kernels for: use_rnn)
+        self._fresh_runtime_state()
+        self._get_dims()       # (refuses what the library has no float64 kernels for: use_rnn)
 
         self.ode_f = models.ODEFunc(input_size, hidden_size, ode_nn, dropout_rate, bias,
                                     input_current_t=self.input_current_t)
@@ -185,55 +154,25 @@ class NJODE64(torch.nn.Module):
                     slots.append((m.bias, m.out_features, (m.out_features,)))
         return slots
 
-    def _views_in_place(self):
-        if self._flat is None:
-            return False
-        base = self._flat.data_ptr()
-        return all(p.dtype == torch.float64 and p.data_ptr() == base + 8 * off
-                   for p, (off, _, _) in zip(self._flat_params, self._param_slices))
+    def _fresh_runtime_state(self):
+        self._schedules = ScheduleCache(16, make=Schedule64)
 
-    def _ensure_flat(self):
-        """Every parameter a float64 view of one flat vector (values are kept; a parameter of another
-        dtype is converted).  Re-done after ``.to()`` / ``.cuda()`` moved the parameters."""
-        if self._views_in_place():
-            return
-        slots = self._flat_slots()
-        dev = slots[0][0].device
-        flat = torch.zeros(sum(n for _, n, _ in slots), dtype=torch.float64, device=dev)
-        slices, params, off = [], [], 0
-        for p, n, shape in slots:
-            if p is not None:
-                flat[off:off + n].copy_(p.data.reshape(-1).to(torch.float64))
-                p.data = flat[off:off + n].view(shape)
-                slices.append((off, n, shape))
-                params.append(p)
-            off += n
-        self._flat, self._param_slices, self._flat_params = flat, slices, params
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        if getattr(self, '_flat', None) is not None:
-            self._ensure_flat()
-        return out
-
-    def _split_flat(self, flat):
-        return [flat[off:off + n].view(shape) for (off, n, shape) in self._param_slices]
-
-    def flat_parameters(self):
-        """The flat float64 vector all parameters are views of."""
-        self._ensure_flat()
-        return self._flat
-
-    def __deepcopy__(self, memo):
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        skip = ('_flat', '_param_slices', '_flat_params', '_ring', '_schedules')
-        import copy
-        for k, v in self.__dict__.items():
-            new.__dict__[k] = None if k in skip else copy.deepcopy(v, memo)
-        new._schedules = collections.OrderedDict()
-        new._ensure_flat()
-        return new
+    def _backward_into(self, call, grads, grad_flat):
+        """``njode_backward_f64`` of a saved forward: the exact discrete adjoint."""
+        weight, has_loss = call.extra
+        grad_loss, grad_hT = grads if has_loss else (None, grads[0])
+        dev = call.flat.device
+        B, H = call.sizes[0], self.hidden_size
+        gl = gh = None
+        if has_loss:
+            gl = (torch.zeros(1, dtype=torch.float64, device=dev) if grad_loss is None
+                  else grad_loss.to(device=dev, dtype=torch.float64).reshape(1).contiguous())
+        if grad_hT is not None:
+            gh = grad_hT.to(device=dev, dtype=torch.float64).reshape(B, H).contiguous()
+        _lib.check(_lib.lib().njode_backward_f64(
+            ctypes.byref(call.dims), call.flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
+            call.flags, weight, _lib.ptr_arg(gl), _lib.ptr_arg(gh), grad_flat.data_ptr(),
+            call.ws.data_ptr(), call.ws.numel(), _lib.stream_arg(dev)))
 
     # -- reference API ----------------------------------------------------------------------------
     def weight_decay_step(self):
@@ -241,18 +180,6 @@ class NJODE64(torch.nn.Module):
         inc = (self.weight - 0.5)
         self.weight = 0.5 + inc * self.weight_decay
         return self.weight
-
-    def _schedule(self, times, delta_t, T, until_T):
-        times = np.ascontiguousarray(times, dtype=np.float64)
-        key = (times.tobytes(), float(delta_t), float(T), bool(until_T))
-        s = self._schedules.get(key)
-        if s is None:
-            s = self._schedules[key] = Schedule64(times, delta_t, T, until_T)
-            if len(self._schedules) > 16:
-                self._schedules.popitem(last=False)
-        else:
-            self._schedules.move_to_end(key)
-        return s
 
     def forward(self, times, time_ptr, X, obs_idx, delta_t, T, start_X, n_obs_ot,
                 return_path=False, get_loss=True, until_T=False, M=None):
@@ -276,7 +203,7 @@ class NJODE64(torch.nn.Module):
         if return_path:
             trainable = False       # (the reference's evaluation calls; a path call saves nothing)
         B = int(start_X.shape[0])
-        sched = self._schedule(times, delta_t, T, until_T)
+        sched = self._schedules.get(times, delta_t, T, until_T)
         time_ptr = np.asarray(time_ptr, dtype=np.int32)
         assert len(times) + 1 == len(time_ptr)
         n_obs = int(time_ptr[-1])
@@ -294,8 +221,8 @@ class NJODE64(torch.nn.Module):
             n_d = n_obs_ot.to(device=dev, dtype=torch.int32).contiguous()
             keep.append(n_d)
 
-        call = _Call64()
-        call.dims, call.weight, call.has_loss = dims, float(self.weight), bool(get_loss)
+        call = _SlabCall()
+        call.dims, call.keep, call.extra = dims, keep, (float(self.weight), bool(get_loss))
         call.batch = _lib.NjodeBatch64(B, n_obs, start_X.data_ptr(), X.data_ptr() if n_obs else None,
                                        M_d.data_ptr() if (M_d is not None and n_obs) else None,
                                        idx.data_ptr() if n_obs else None,
@@ -303,33 +230,21 @@ class NJODE64(torch.nn.Module):
         call.flags = ((_lib.C_GET_LOSS if get_loss else 0) | (_lib.C_RETURN_PATH if return_path else 0)
                       | (_lib.C_SAVE_BWD if trainable else 0))
         call.sizes = (B, n_obs, sched.n_times, sched.n_steps)
-        if self._ring is None:
-            self._ring = PinnedRing()
-        slot, pinned = self._ring.acquire(sched.packed_nbytes())
-        call.sched = sched.pack_into(pinned.numpy(), time_ptr)
         L = _lib.lib()
-        need = ctypes.c_size_t(0)
-        _lib.check(L.njode_f64_workspace_bytes(ctypes.byref(dims), *call.sizes, call.flags, ctypes.byref(need)))
-        call.ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        call.keep, call.flat = keep, self._flat
-
-        hT = torch.empty(B, self.hidden_size, dtype=f64, device=dev)
-        loss = torch.zeros(1, dtype=f64, device=dev) if get_loss else None
-        path_h = path_y = None
-        if return_path:
-            path_h = torch.empty(sched.n_rows, B, self.hidden_size, dtype=f64, device=dev)
-            path_y = torch.empty(sched.n_rows, B, self.output_size, dtype=f64, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        try:
+        with issuing(self, call, sched, time_ptr, L.njode_f64_workspace_bytes) as stream:
+            hT = torch.empty(B, self.hidden_size, dtype=f64, device=dev)
+            loss = torch.zeros(1, dtype=f64, device=dev) if get_loss else None
+            path_h = path_y = None
+            if return_path:
+                path_h = torch.empty(sched.n_rows, B, self.hidden_size, dtype=f64, device=dev)
+                path_y = torch.empty(sched.n_rows, B, self.output_size, dtype=f64, device=dev)
             rc = L.njode_forward_f64(
                 ctypes.byref(dims), self._flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
-                call.flags, call.weight, hT.data_ptr(), _lib.ptr_arg(loss), _lib.ptr_arg(path_h),
+                call.flags, call.extra[0], hT.data_ptr(), _lib.ptr_arg(loss), _lib.ptr_arg(path_h),
                 _lib.ptr_arg(path_y), call.ws.data_ptr(), call.ws.numel(), stream.cuda_stream)
-        finally:
-            self._ring.release_after(slot, stream)      # (the pinned schedule: free once the stream passed)
         _lib.check(rc)
         if trainable:
-            outs = _NJODE64Function.apply(self, call, (loss, hT) if get_loss else (hT,), *self._flat_params)
+            outs = _SlabFunction.apply(self, call, (loss, hT) if get_loss else (hT,), *self._flat_params)
             loss, hT = outs if get_loss else (None, outs[0])
         loss_out = loss.reshape(()) if get_loss else 0
         if get_loss and not self.device_outputs:

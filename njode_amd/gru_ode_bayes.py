@@ -24,7 +24,6 @@ counter.  Options ``dropout_seed`` and ``device_outputs`` (keep the losses on th
 returns them on the CPU, where the reference harness calls ``.numpy()``) are read from the keyword
 ``options``, as ``models.NJODE`` reads them.
 """
-import copy
 import ctypes
 import math
 
@@ -32,7 +31,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .schedule import PinnedRing, ScheduleCache
+from ._flat import FlatVector
+from ._slabcall import _SlabCall, _SlabFunction, issuing
+from .schedule import ScheduleCache
 
 
 def init_weights(m):
@@ -68,48 +69,11 @@ class _ObservationCell(torch.nn.Module):
         self.bias_prep = torch.nn.Parameter(0.1 + torch.zeros(input_size, prep_hidden))
 
 
-class _Call:
-    """One forward call: structs, flags, the buffers they point into and the workspace, kept alive
-    for the backward."""
-    __slots__ = ('dims', 'batch', 'sched', 'flags', 'mixing', 'p_drop', 'seed', 'ws', 'keep', 'sizes', 'flat')
-
-
-class _GOBFunction(torch.autograd.Function):
-    """(losses, hT) = F(params): ``losses = [loss, loss_1]``; backward = the exact discrete adjoint
-    (``njode_gob_backward_f32``)."""
-
-    @staticmethod
-    def forward(ctx, model, call, outs, *params):
-        ctx.model, ctx.call = model, call
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(*params)
-        return outs
-
-    @staticmethod
-    def backward(ctx, grad_losses, grad_hT):
-        model, call = ctx.model, ctx.call
-        ctx.saved_tensors       # (autograd's own check: the parameters are the forward's)
-        if call.flat is not model._flat:
-            raise RuntimeError('the parameters of this forward were moved before its backward')
-        dev = call.flat.device
-        B, H = call.sizes[0], model.hidden_size
-        gl = (torch.zeros(2, dtype=torch.float32, device=dev) if grad_losses is None
-              else grad_losses.to(device=dev, dtype=torch.float32).reshape(2).contiguous())
-        gh = None
-        if grad_hT is not None:
-            gh = grad_hT.to(device=dev, dtype=torch.float32).reshape(B, H).contiguous()
-        grad_flat = torch.empty_like(call.flat)
-        _lib.check(_lib.lib().njode_gob_backward_f32(
-            ctypes.byref(call.dims), call.flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
-            call.flags, call.mixing, call.p_drop, call.seed, gl.data_ptr(), gl.data_ptr() + 4,
-            _lib.ptr_arg(gh), grad_flat.data_ptr(), call.ws.data_ptr(), call.ws.numel(),
-            _lib.stream_arg(dev)))
-        return (None, None, None) + tuple(model._split_flat(grad_flat))
-
-
-class NNFOwithBayesianJumps(torch.nn.Module):
+class NNFOwithBayesianJumps(FlatVector, torch.nn.Module):
     """Neural negative feedback ODE with Bayesian jumps on the GPU; the interface of the
-    reference's class of the same name."""
+    reference's class of the same name.  The autograd node of a saved forward (``_SlabFunction``)
+    has the outputs (losses, hT), ``losses = [loss, loss_1]``."""
+    _moved_error = 'the parameters of this forward were moved before its backward'
 
     def __init__(self, input_size, hidden_size, p_hidden, prep_hidden, bias=True, cov_size=1, cov_hidden=1,
                  classification_hidden=1, logvar=True, mixing=1, dropout_rate=0, full_gru_ode=False,
@@ -147,8 +111,8 @@ class NNFOwithBayesianJumps(torch.nn.Module):
         self.seed = int(options1.get('dropout_seed', options.get('dropout_seed', 0)))
         self._step_counter = 0
         self._flat = self._param_slices = self._flat_params = self._dims = self._ring = None
-        self._schedules = ScheduleCache(16)
-        self._get_dims()        # (refuses what the library has no kernels for)
+        self._fresh_runtime_state()
+        self._get_dims()       # (refuses what the library has no kernels for)
 
         self.p_model = torch.nn.Sequential(
             torch.nn.Linear(hidden_size, p_hidden, bias=bias), torch.nn.ReLU(),
@@ -208,55 +172,31 @@ class NNFOwithBayesianJumps(torch.nn.Module):
         linear(self.covariates_map[3])
         return slots
 
-    def _views_in_place(self):
-        if self._flat is None:
-            return False
-        base = self._flat.data_ptr()
-        return all(p.dtype == torch.float32 and p.data_ptr() == base + 4 * off
-                   for p, (off, _, _) in zip(self._flat_params, self._param_slices))
-
     def _ensure_flat(self):
-        """Every kernel parameter an fp32 view of one flat vector (values are kept).  Re-done after
-        ``.to()`` / ``.cuda()`` moved the parameters."""
-        if self._views_in_place():
-            return
-        slots = self._flat_slots()
-        dev = slots[0][0].device
-        flat = torch.zeros(sum(n for _, n, _ in slots), dtype=torch.float32, device=dev)
-        slices, params, off = [], [], 0
-        for p, n, shape in slots:
-            if p is not None:
-                flat[off:off + n].copy_(p.data.reshape(-1).to(torch.float32))
-                p.data = flat[off:off + n].view(shape)
-                slices.append((off, n, shape))
-                params.append(p)
-            off += n
-        assert off == _lib.lib().njode_gob_param_count(ctypes.byref(self._get_dims()))
-        self._flat, self._param_slices, self._flat_params = flat, slices, params
+        flat = self._flat
+        super()._ensure_flat()
+        if self._flat is not flat:      # (laid out anew: the library counts the same slots)
+            assert self._flat.numel() == _lib.lib().njode_gob_param_count(ctypes.byref(self._get_dims()))
 
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        if getattr(self, '_flat', None) is not None:
-            self._ensure_flat()
-        return out
+    def _fresh_runtime_state(self):
+        self._schedules = ScheduleCache(16)
 
-    def _split_flat(self, flat):
-        return [flat[off:off + n].view(shape) for (off, n, shape) in self._param_slices]
-
-    def flat_parameters(self):
-        """The flat fp32 vector the kernels' parameters are views of."""
-        self._ensure_flat()
-        return self._flat
-
-    def __deepcopy__(self, memo):
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        skip = ('_flat', '_param_slices', '_flat_params', '_ring', '_schedules')
-        for k, v in self.__dict__.items():
-            new.__dict__[k] = None if k in skip else copy.deepcopy(v, memo)
-        new._schedules = ScheduleCache(16)
-        new._ensure_flat()
-        return new
+    def _backward_into(self, call, grads, grad_flat):
+        """``njode_gob_backward_f32`` of a saved forward: the exact discrete adjoint."""
+        grad_losses, grad_hT = grads
+        mixing, p_drop, seed = call.extra
+        dev = call.flat.device
+        B, H = call.sizes[0], self.hidden_size
+        gl = (torch.zeros(2, dtype=torch.float32, device=dev) if grad_losses is None
+              else grad_losses.to(device=dev, dtype=torch.float32).reshape(2).contiguous())
+        gh = None
+        if grad_hT is not None:
+            gh = grad_hT.to(device=dev, dtype=torch.float32).reshape(B, H).contiguous()
+        _lib.check(_lib.lib().njode_gob_backward_f32(
+            ctypes.byref(call.dims), call.flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
+            call.flags, mixing, p_drop, seed, gl.data_ptr(), gl.data_ptr() + 4,
+            _lib.ptr_arg(gh), grad_flat.data_ptr(), call.ws.data_ptr(), call.ws.numel(),
+            _lib.stream_arg(dev)))
 
     # -- reference API ----------------------------------------------------------------------------
     def weight_decay_step(self):
@@ -293,47 +233,35 @@ class NNFOwithBayesianJumps(torch.nn.Module):
         idx = torch.as_tensor(obs_idx).to(device=dev, dtype=torch.int32).contiguous()
         assert cov.shape[1] == self.input_size and X.shape[0] >= n_obs and M.shape == X.shape
 
-        call = _Call()
-        call.dims, call.mixing, call.p_drop = dims, float(self.mixing), self.dropout_rate
+        call = _SlabCall()
+        call.dims, call.keep = dims, [cov, X, M, idx]
         call.batch = _lib.NjodeBatch(B, n_obs, cov.data_ptr(), X.data_ptr() if n_obs else None,
                                      M.data_ptr() if n_obs else None, idx.data_ptr() if n_obs else None,
                                      None, float(B), 0, None, None)
         call.flags = ((_lib.C_TRAIN if self.training else 0) | (_lib.C_RETURN_PATH if return_path else 0)
                       | (_lib.C_SAVE_BWD if trainable else 0))
         call.sizes = (B, n_obs, sched.n_times, sched.n_steps)
-        call.seed = (self.seed * 0x9E3779B97F4A7C15 + self._step_counter) & 0xFFFFFFFFFFFFFFFF
+        seed = (self.seed * 0x9E3779B97F4A7C15 + self._step_counter) & 0xFFFFFFFFFFFFFFFF
+        call.extra = (float(self.mixing), self.dropout_rate, seed)
         if self.training:
             self._step_counter += 1
-        if self._ring is None:
-            self._ring = PinnedRing()
-        slot, pinned = self._ring.acquire(sched.packed_nbytes())
-        sched.pack_into(pinned.numpy(), time_ptr)
-        call.sched = sched.struct(pinned.data_ptr())
         L = _lib.lib()
-        need = ctypes.c_size_t(0)
-        _lib.check(L.njode_gob_workspace_bytes(ctypes.byref(dims), *call.sizes, call.flags, ctypes.byref(need)))
-        call.ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        call.keep, call.flat = [cov, X, M, idx], self._flat
-
         H, D2 = self.hidden_size, 2 * self.input_size
-        hT = torch.empty(B, H, dtype=f32, device=dev)
-        losses = torch.empty(2, dtype=f32, device=dev)
-        path_h = path_p = None
-        if return_path:
-            path_h = torch.empty(sched.n_rows, B, H, dtype=f32, device=dev)
-            path_p = torch.empty(sched.n_rows, B, D2, dtype=f32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        try:
+        with issuing(self, call, sched, time_ptr, L.njode_gob_workspace_bytes) as stream:
+            hT = torch.empty(B, H, dtype=f32, device=dev)
+            losses = torch.empty(2, dtype=f32, device=dev)
+            path_h = path_p = None
+            if return_path:
+                path_h = torch.empty(sched.n_rows, B, H, dtype=f32, device=dev)
+                path_p = torch.empty(sched.n_rows, B, D2, dtype=f32, device=dev)
             rc = L.njode_gob_forward_f32(
                 ctypes.byref(dims), self._flat.data_ptr(), ctypes.byref(call.batch), ctypes.byref(call.sched),
-                call.flags, call.mixing, call.p_drop, call.seed, hT.data_ptr(), losses.data_ptr(),
+                call.flags, *call.extra, hT.data_ptr(), losses.data_ptr(),
                 _lib.ptr_arg(path_h), _lib.ptr_arg(path_p), call.ws.data_ptr(), call.ws.numel(),
                 stream.cuda_stream)
-        finally:
-            self._ring.release_after(slot, stream)      # (the pinned schedule: free once the stream passed)
         _lib.check(rc)
         if trainable:
-            losses, hT = _GOBFunction.apply(self, call, (losses, hT), *self._flat_params)
+            losses, hT = _SlabFunction.apply(self, call, (losses, hT), *self._flat_params)
         loss, loss_1 = losses[0], losses[1]
         if not self.device_outputs:
             loss, loss_1 = loss.cpu(), loss_1.cpu()

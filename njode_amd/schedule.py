@@ -186,10 +186,10 @@ def cond_exp_clock(times, delta_t, T, stage_maturities=None):
 
 
 class ScheduleCache:
-    """LRU of schedules keyed by (times, delta_t, T, until_T)."""
+    """LRU of schedules keyed by (times, delta_t, T, until_T); ``make``: the schedule class."""
 
-    def __init__(self, capacity=64):
-        self.capacity = capacity
+    def __init__(self, capacity=64, make=Schedule):
+        self.capacity, self.make = capacity, make
         self._d = collections.OrderedDict()
 
     def get(self, times, delta_t, T, until_T):
@@ -197,7 +197,7 @@ class ScheduleCache:
         key = (times.tobytes(), float(delta_t), float(T), bool(until_T))
         s = self._d.get(key)
         if s is None:
-            s = Schedule(times, delta_t, T, until_T)
+            s = self.make(times, delta_t, T, until_T)
             self._d[key] = s
             if len(self._d) > self.capacity:
                 self._d.popitem(last=False)

@@ -15,8 +15,8 @@ MAX_HIDDEN = _lib.MAX_HIDDEN
 LDS_LIMIT = 160 * 1024
 MAX_SLABS = 2048
 SLAB_BUDGET = 1 << 30
-LOSS_THREADS = 256                          # k_f64_loss: one workgroup, striding over the paths
-CLEAR_ELEMS = 2048 * 256                    # k_f64_rows_clear: the grid's cap, striding beyond it
+LOSS_THREADS = 256                          # tree_sum_256: one workgroup, striding over the paths
+CLEAR_ELEMS = 2048 * 256                    # k_rows_clear: the grid's cap, striding beyond it
 
 R_RNN = 'use_rnn: the GRU jump has no float64 kernels'
 R_SIZES = 'sizes out of range'

@@ -38,7 +38,7 @@ this module that fail, and whether ``test_hip_f64_route.py`` notices:
       the existing module passes (51 of 51).
   (b) ``lamx`` reset for a workgroup's first path only: ``test_max_slabs_masked``; the existing module
       passes.
-  (c) ``k_f64_loss`` reads the first 256 partials only: ``test_max_slabs_unmasked``,
+  (c) ``tree_sum_256`` (under ``k_f64_loss``) reads the first 256 partials only: ``test_max_slabs_unmasked``,
       ``test_max_slabs_masked``, ``test_row_table_beyond_the_clear_grid``; the existing module passes.
   (d) ``res_bwd`` case 2 without the division by ``mult``: 19 tests (every training row with the
       readout's case 2, trivial chunks included, both ``masked_res`` rows); the existing module fails
@@ -209,7 +209,7 @@ def test_slab_byte_budget():
 
 
 def test_row_table_beyond_the_clear_grid():
-    """250 observation times x 2 100 paths: ``k_f64_rows_clear`` strides.  Loss, hT, gradients."""
+    """250 observation times x 2 100 paths: ``k_rows_clear`` strides.  Loss, hT, gradients."""
     cfg, b, dt, T, until, lab = _case('slab/rows_clear')
     assert {'rows_clear_strided', 'S_max_slabs', 'loss_tree_strided'} <= lab
     _train('slab/rows_clear', cfg, _init_sd(cfg, 1), b, dt, T, until)
