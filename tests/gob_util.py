@@ -47,10 +47,26 @@ def model_kwargs(cfg, dropout_rate=0.0, bias=True, **options):
                 full_gru_ode=True, solver='euler', impute=cfg['impute'], **options)
 
 
+def objective_of(objective, loss, loss_1, hT, c_hT):
+    """The scalar a test differentiates: ``objective`` is 'loss', 'loss_1' or a pair (a, b) for
+    a * loss + b * loss_1 (a term whose weight is 0 is left out of the graph); ``c_hT`` (a tensor like
+    ``hT`` or None) adds <c_hT, hT>."""
+    if isinstance(objective, str):
+        terms = [{'loss': loss, 'loss_1': loss_1}[objective]]
+    else:
+        a, b = objective
+        terms = ([a * loss] if a else []) + ([b * loss_1] if b else [])
+    if c_hT is not None:
+        terms.append((c_hT * hT).sum())
+    assert terms, 'an objective of no terms'
+    return sum(terms[1:], terms[0])
+
+
 def restate(sd, b, mixing, dtype, grads=True, masks=None, c_hT=None, objective='loss', return_path=False,
             device=None):
     """The restatement in ``dtype``: dict of float64 numpy arrays hT, loss, loss_1[, path_p, path_h]
-    and g (gradients of ``objective`` [+ <c_hT, hT>] per loss parameter)."""
+    and g (gradients of ``objective`` [+ <c_hT, hT>] per loss parameter; ``objective``: see
+    ``objective_of``)."""
     threads = torch.get_num_threads()
     torch.set_num_threads(1)
     try:
@@ -64,9 +80,8 @@ def restate(sd, b, mixing, dtype, grads=True, masks=None, c_hT=None, objective='
         if return_path:
             res['path_t'] = out['path_t']
         if grads:
-            obj = out[objective]
-            if c_hT is not None:
-                obj = obj + (torch.as_tensor(c_hT).to(dtype=dtype, device=device) * out['hT']).sum()
+            c = None if c_hT is None else torch.as_tensor(c_hT).to(dtype=dtype, device=device)
+            obj = objective_of(objective, out['loss'], out['loss_1'], out['hT'], c)
             keys = gob_oracle.loss_keys(p)
             gs = torch.autograd.grad(obj, [p[k] for k in keys], allow_unused=True)
             res['g'] = {k: (np.zeros(tuple(p[k].shape)) if g is None else g.cpu().numpy().astype(np.float64))

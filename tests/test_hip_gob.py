@@ -48,7 +48,8 @@ FLOOR_H, FLOOR_G, FLOOR_L = 2e-6, 1e-5, 1e-6
 
 
 def hip_run(m, b, objective='loss', c_hT=None, return_path=False, grads=True):
-    """dict of float64 numpy results of one HIP call: hT, loss, loss_1[, path_p, path_h][, g]."""
+    """dict of float64 numpy results of one HIP call: hT, loss, loss_1[, path_p, path_h][, g];
+    ``objective``: 'loss', 'loss_1' or (a, b) for a * loss + b * loss_1 (``gob_util.objective_of``)."""
     m.zero_grad(set_to_none=True)
     if return_path:
         with torch.no_grad():
@@ -61,10 +62,8 @@ def hip_run(m, b, objective='loss', c_hT=None, return_path=False, grads=True):
     assert class_pred.shape == (hT.shape[0], 1)
     res = dict(hT=hT.detach().cpu().numpy().astype(np.float64), loss=float(loss.detach()), loss_1=float(loss_1.detach()))
     if grads:
-        obj = loss if objective == 'loss' else loss_1
-        if c_hT is not None:
-            obj = obj + (torch.as_tensor(c_hT, dtype=torch.float32, device=hT.device) * hT).sum()
-        obj.backward()
+        c = None if c_hT is None else torch.as_tensor(c_hT, dtype=torch.float32, device=hT.device)
+        gob_util.objective_of(objective, loss, loss_1, hT, c).backward()
         res['g'] = {}
         for k, p in m.named_parameters():
             if k.startswith(gob_util.SKIP):
@@ -406,12 +405,15 @@ def test_train_two_epochs_checkpoint_and_resume(tmp_path):
 
 # ---- 9. the C ABI -------------------------------------------------------------------------------------
 
-def abi_call(name, phase):
-    """Forward (TRAIN | RETURN_PATH | SAVE_BWD) and backward of a golden case through the C ABI with
-    every buffer at exactly its stated size between guard bands."""
+def golden_abi(name):
+    """(cfg, state dict, batch) of a golden case, as ``abi_call`` takes them."""
     g = golden(name)
-    b, cfg = golden_batch(g), golden_cfg(g)
-    sd = part(g, 'sd.')
+    return golden_cfg(g), part(g, 'sd.'), golden_batch(g)
+
+
+def abi_call(cfg, sd, b, phase, min_guard=None):
+    """Forward (TRAIN | RETURN_PATH | SAVE_BWD) and backward of a model (with bias slots) on a batch
+    through the C ABI with every buffer at exactly its stated size between guard bands."""
     L = _lib.lib()
     dims = _lib.NjodeGobDims(cfg['input_size'], cfg['hidden_size'], cfg['p_hidden'], cfg['prep_hidden'],
                              cfg['cov_hidden'], _lib.GOB_F_BIAS | (_lib.GOB_F_IMPUTE if cfg['impute'] else 0))
@@ -425,7 +427,7 @@ def abi_call(name, phase):
     need = ctypes.c_size_t(0)
     _lib.check(L.njode_gob_workspace_bytes(ctypes.byref(dims), B, n_obs, sched.n_times, sched.n_steps, flags,
                                            ctypes.byref(need)))
-    A = guarded.Arena(phase=phase)
+    A = guarded.Arena(phase=phase, min_guard=min_guard)
     A.add('params', flat.nbytes, 'nan32').add('start_X', B * D * 4, 'nan32').add('X', n_obs * D * 4, 'nan32')
     A.add('M', n_obs * D * 4, 'nan32').add('obs_idx', n_obs * 4, 'index', modulo=B)
     A.add('hT', B * H * 4).add('loss', 8).add('path_h', sched.n_rows * B * H * 4)
@@ -456,7 +458,7 @@ def abi_call(name, phase):
 
 
 def test_abi_refusals_are_made_before_launch():
-    A, fwd, bwd, need, _ = abi_call('gob_d1_impute', 0)
+    A, fwd, bwd, need, _ = abi_call(*golden_abi('gob_d1_impute'), 0)
     before = A.mem.clone()
     E = _lib.E_BADARG
     assert fwd(params=None) == E and fwd(batch=None) == E and fwd(sched=None) == E and fwd(hT=None) == E
@@ -474,7 +476,7 @@ def test_abi_refusals_are_made_before_launch():
 def test_abi_stays_inside_buffers_of_exactly_the_stated_size(name):
     outs = []
     for phase in (0, 1):
-        A, fwd, bwd, need, (B, H, D, n_rows, P) = abi_call(name, phase)
+        A, fwd, bwd, need, (B, H, D, n_rows, P) = abi_call(*golden_abi(name), phase)
         assert fwd() == 0, _lib.lib().njode_last_error()
         assert bwd() == 0, _lib.lib().njode_last_error()
         assert A.check() == []
